@@ -16,7 +16,20 @@ makes to reach the same plan of every candidate (findSpotNodeForPod stops at
 the first fit).  The dense-equivalent rate (every candidate pod x every spot
 node) is reported beside it, labelled as such.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+cluster, prepares the tick, runs one tick with per-candidate outputs (the
+reference-equivalent check count), warms up, times EXACTLY --steps sr_plan_run
+calls and prints the line (metric, value, unit, ms_per_step, ...).  --full adds
+every other measurement to the same line: the per-kernel calibration pass and
+HIP events in the timed region (kernels_ms, roofline), latency_ms, the
+end-to-end and whole-housekeeping ticks (end_to_end_tick,
+drain_plan_latency_ms), the CPU baseline with its plan parity (cpu_baseline)
+and, for N > 1, the weak-scaled tick (weak_scaling); a plain line holds null
+in their places.  --dump-outputs DIR writes what the last timed step returned
+to its caller as DIR/<name>.npy (dump_outputs); the synthetic cluster is
+seeded, so the same arguments give the same inputs in every run and build.
 
 N > 1 runs one process per GPU: under torch.distributed.run (RANK /
 WORLD_SIZE / LOCAL_RANK / MASTER_* from the environment), or, when
@@ -91,6 +104,29 @@ def shard_sizes(n_cand, world):
 
 
 E2E_IDLE = os.environ.get("SR_BENCH_E2E_IDLE", "1") != "0"
+
+# sr_plan_out's scalar fields, in the order of plan_out.npy (--dump-outputs)
+PLAN_OUT_SCALARS = ("winner", "first_ok", "first_fallback", "winner_npods", "checks", "fallback_pods", "checks_dense")
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: what the last timed sr_plan_run handed its caller, as
+    <path>/<name>.npy in float64 (rank r > 0 of an N > 1 job: <name>_rank<r>.npy,
+    its own shard).  plan_out: the sr_plan_out scalars (PLAN_OUT_SCALARS);
+    winner_map: the first drainable candidate's spot position per pod; status
+    and node_of_pod: the optional per-candidate outputs, which the timed step
+    leaves NULL, from the same prepared tick run once more with them asked for.
+    Every value is an integer below 2^53, so float64 holds it exactly.  An array
+    whose share of DUMP_BYTES_MAX is too small is written as a fixed, seeded
+    sample of its elements (in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // (8 * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64).ravel()
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0x5EED).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
 
 
 def latest_profile(name):
@@ -391,9 +427,10 @@ def measure_ticks(lib, checker, sc, rank, world, args):
     """The timed region on one synthetic cluster: its node map and candidate
     lists (run()'s, rescheduler.go:228-264), this rank's shard (c % world), the
     steady-state tick prepared, one full run (K2's bytes, the reference-
-    equivalent checks), the warm-up, the calibration pass, then EXACTLY
-    args.steps sr_plan_run calls bracketed by barrier + synchronize (max over
-    ranks), and the full run once more for the parity check."""
+    equivalent checks), the warm-up, with --full the calibration pass, then
+    EXACTLY args.steps sr_plan_run calls bracketed by barrier + synchronize (max
+    over ranks), and with --full or --dump-outputs the full run once more (the
+    parity check, the dumped per-candidate outputs)."""
     import torch
     import torch.distributed as dist
     nm = new_node_map(lib.sr_new_node_map, sc.ptr, sc.n_nodes, sc.n_pods, sc.od_label, sc.spot_label)
@@ -466,21 +503,24 @@ def measure_ticks(lib, checker, sc, rank, world, args):
     for _ in range(args.warmup):
         assert lib.sr_plan_run(checker.handle, ctypes.byref(out)) == capi.SR_OK, checker.last_error()
 
-    # Calibration (untimed): every kernel bracketed with events -> per-kernel
-    # breakdown and the dominant kernel.
+    # Calibration (untimed, --full): every kernel bracketed with events ->
+    # per-kernel breakdown and the dominant kernel.
     names = ["k0_tables", "k2_placement", "k3_winner", "collective"]
-    checker.set_timing(7)
-    for _ in range(max(5, min(args.steps, 20))):
-        st = lib.sr_plan_run(checker.handle, ctypes.byref(out))
-        assert st == capi.SR_OK, (st, checker.last_error())
-    tm = checker.timing()
-    breakdown = dict(zip(names, [x / max(1, tm.n_runs) for x in
-                                 (tm.ms_tables, tm.ms_placement, tm.ms_winner, tm.ms_collective)]))
-    dom = max(names[:2], key=lambda x: breakdown[x])
-    dom_bit = 1 << names.index(dom)
+    breakdown, dom, dom_bit = {}, None, 0
+    if args.full:
+        checker.set_timing(7)
+        for _ in range(max(5, min(args.steps, 20))):
+            st = lib.sr_plan_run(checker.handle, ctypes.byref(out))
+            assert st == capi.SR_OK, (st, checker.last_error())
+        tm = checker.timing()
+        breakdown = dict(zip(names, [x / max(1, tm.n_runs) for x in
+                                     (tm.ms_tables, tm.ms_placement, tm.ms_winner, tm.ms_collective)]))
+        dom = max(names[:2], key=lambda x: breakdown[x])
+        dom_bit = 1 << names.index(dom)
 
-    # Timed region: K steps, only the dominant kernel bracketed with events.
-    checker.set_timing(0 if args.no_events else dom_bit | (max(1, args.event_every) << 8))
+    # Timed region: K steps; --full brackets the dominant kernel with events.
+    events = args.full and not args.no_events
+    checker.set_timing(dom_bit | (max(1, args.event_every) << 8) if events else 0)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -494,9 +534,14 @@ def measure_ticks(lib, checker, sc, rank, world, args):
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
     assert bad == capi.SR_OK, (bad, checker.last_error())  # a failing run must not be timed as a fast step
+    # what the last timed step handed its caller (--dump-outputs)
+    last = {"plan_out": np.array([getattr(out, k) for k in PLAN_OUT_SCALARS], np.float64),
+            "winner_map": wmap[:max(0, int(out.winner_npods))].astype(np.float64)}
     tm = checker.timing()
-    dom_ms = ([tm.ms_tables, tm.ms_placement][names.index(dom)] / max(1, tm.n_runs) if not args.no_events
-              else breakdown[dom])
+    dom_ms = None
+    if args.full:
+        dom_ms = ([tm.ms_tables, tm.ms_placement][names.index(dom)] / max(1, tm.n_runs) if events
+                  else breakdown[dom])
     checker.set_timing(0)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -510,12 +555,15 @@ def measure_ticks(lib, checker, sc, rank, world, args):
     per_rank = gather_per_rank(rank_record(rank, len(loff) - 1, len(lpods), local_elapsed, args.steps, breakdown),
                                world)
 
-    # per-candidate outputs once more (outside the timed region): the parity
-    # check and K2's byte counts of the same plan
-    st = lib.sr_plan_run(checker.handle, ctypes.byref(full))
-    assert st == capi.SR_OK, (st, checker.last_error())
+    # per-candidate outputs once more (outside the timed region; --full or
+    # --dump-outputs): the parity check and K2's byte counts of the same plan
+    if args.full or args.dump_outputs:
+        st = lib.sr_plan_run(checker.handle, ctypes.byref(full))
+        assert st == capi.SR_OK, (st, checker.last_error())
+        last["status"] = status[:len(loff) - 1].astype(np.float64)
+        last["node_of_pod"] = nodes_out[:len(lpods)].astype(np.float64)
     tm = checker.timing()
-    return dict(nm=nm, cand_off=cand_off, cand_pods=cand_pods, loff=loff, lpods=lpods, gidx=gidx, snap=snap,
+    return dict(last=last, nm=nm, cand_off=cand_off, cand_pods=cand_pods, loff=loff, lpods=lpods, gidx=gidx, snap=snap,
                 cands=cands, out=out, wmap=wmap, full=full, status=status, nodes_out=nodes_out, mutation=mutation, steady=steady,
                 pfd_ms=pfd_ms, pack_ms=pack_ms, breakdown=breakdown, dom=dom, dom_ms=dom_ms, elapsed=elapsed,
                 total_issued=total_issued, total_dense=total_dense, tm=tm, issued_local=issued_local,
@@ -528,6 +576,13 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=3, choices=[1, 2, 3, 4, 5])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel calibration and roofline, latency_ms, the end-to-end "
+                         "ticks, the CPU baseline and its plan parity, the weak-scaled tick for N > 1 "
+                         "(--no-weak-beside, --cpu-seconds, --e2e-reps, --no-cpu-baseline, --no-events and "
+                         "--event-every apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--variant", default="baseline", choices=["baseline", "realistic", "affinity"],
                     help="realistic: the config with StatefulSet volumes, init containers and GPU pods; affinity: "
                          "Deployments with hostname anti-affinity and zone topology spread (both report the "
@@ -596,15 +651,27 @@ def main():
     variant_kw = {"realistic": REALISTIC, "affinity": AFFINITY}.get(args.variant, {})
     sc = SynthCluster(args.config, n_on_demand=cluster_on_demand(args.config, world, args.scaling), **variant_kw)
     M = measure_ticks(lib, checker, sc, rank, world, args)
-    # (loff / lpods / gidx stay referenced: `cands` points into them)
-    nm, cand_off, cand_pods, loff, lpods = M["nm"], M["cand_off"], M["cand_pods"], M["loff"], M["lpods"]
-    gidx = M["gidx"]  # noqa: F841
-    snap, cands, out, wmap, full = M["snap"], M["cands"], M["out"], M["wmap"], M["full"]
-    status, nodes_out, mutation, steady = M["status"], M["nodes_out"], M["mutation"], M["steady"]
-    pfd_ms, pack_ms, breakdown, dom, dom_ms = M["pfd_ms"], M["pack_ms"], M["breakdown"], M["dom"], M["dom_ms"]
-    elapsed, total_issued, total_dense, tm = M["elapsed"], M["total_issued"], M["total_dense"], M["tm"]
-    issued_local, per_rank, mut_pod, mut_pos = M["issued_local"], M["per_rank"], M["mut_pod"], M["mut_pos"]
-    ms_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, M["last"], rank)
+    lat, end_to_end, weak_scaling = [], None, None
+    if args.full:
+        lat, end_to_end, weak_scaling = full_measurements(lib, checker, sc, M, rank, world, args, variant_kw)
+    report(sc, M, rank, world, args, transport, lat, end_to_end, weak_scaling)
+    lib.sr_snapshot_destroy(M["snap"])
+    checker.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(lib, checker, sc, M, rank, world, args, variant_kw):
+    """--full, after the timed steps: the idle-device tick latency, the
+    end-to-end and whole-housekeeping ticks and, for N > 1 with --scaling
+    strong, the weak-scaled tick.  Returns (lat, end_to_end, weak_scaling)."""
+    import torch
+    # (loff / lpods / gidx stay referenced in M: `cands` points into them)
+    nm, loff = M["nm"], M["loff"]
+    cands, out, wmap, full = M["cands"], M["out"], M["wmap"], M["full"]
+    nodes_out, pfd_ms, mut_pod, mut_pos = M["nodes_out"], M["pfd_ms"], M["mut_pod"], M["mut_pos"]
 
     # Result latency of one tick on an idle device: sr_plan_run from the launch
     # to the winner and its mapping in host memory.  On one rank the run returns
@@ -835,8 +902,20 @@ def main():
             "note": "not the line's value: N x the config's candidates over the same spot pool (weak scaling), "
                     "measured after the line in the same job"}
         lib.sr_snapshot_destroy(W["snap"])
+    return lat, end_to_end, weak_scaling
 
-    if rank == 0:
+
+def report(sc, M, rank, world, args, transport, lat, end_to_end, weak_scaling):
+    """Rank 0 prints the JSON line: the headline figure and this run's workload;
+    what only --full measures is null in a plain line."""
+    nm, cand_off, cand_pods, loff, lpods = M["nm"], M["cand_off"], M["cand_pods"], M["loff"], M["lpods"]
+    out, status, nodes_out, mutation, steady = M["out"], M["status"], M["nodes_out"], M["mutation"], M["steady"]
+    pfd_ms, pack_ms, breakdown, dom, dom_ms = M["pfd_ms"], M["pack_ms"], M["breakdown"], M["dom"], M["dom_ms"]
+    elapsed, total_issued, total_dense, tm = M["elapsed"], M["total_issued"], M["total_dense"], M["tm"]
+    issued_local, per_rank = M["issued_local"], M["per_rank"]
+    ms_step = 1e3 * elapsed / args.steps
+
+    if rank == 0 and args.full:  # the roofline's inputs
         alg = {"k2_placement": tm.bytes_placement, "k0_tables": tm.bytes_tables}[dom]
         achieved = alg / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         # PMC traffic of the same kernel on this config and variant, from the
@@ -860,6 +939,7 @@ def main():
                                   "(tools/gpu_round.sh); not measured in this run"}
         chain = k2_chain_summary(latest_profile("c%d%s_k2_wave_profile.txt"
                                                 % (args.config, "" if args.variant == "baseline" else "_" + args.variant)))
+    if rank == 0:
         line = {
             "metric": "reference-equivalent pod x spot-node feasibility checks/s (drain-plan latency: "
                       "drain_plan_latency_ms)",
@@ -871,7 +951,8 @@ def main():
                                         "the same plan of every candidate (value); dense_equivalent = candidate "
                                         "pods x spot nodes (notional, not work done)"},
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step, "latency_ms": round(float(np.median(lat)), 5),
+            "ms_per_step": ms_step, "full": bool(args.full),
+            "latency_ms": round(float(np.median(lat)), 5) if lat else None,
             "drain_plan_latency_ms": end_to_end["median_ms"] if end_to_end else None,
             "drain_plan_latency_span": "host to host, SURVEY 8(d): sr_plan_first on a fresh snapshot with one spot "
                                        "node changed (encode + H2D + kernels + winner and mapping on the host); "
@@ -905,7 +986,7 @@ def main():
             if world > 1 else None,
             "first_ok": int(out.first_ok), "winner": int(out.winner),
             "fallback_candidates": int(np.sum(status[:len(loff) - 1] == capi.SR_CAND_FALLBACK)),
-            "kernels_ms": {kk: round(v, 5) for kk, v in breakdown.items()},
+            "kernels_ms": {kk: round(v, 5) for kk, v in breakdown.items()} if args.full else None,
             "workload_rows": {"static_classes": tm.n_rows_static, "threshold_rows": tm.n_rows_threshold,
                               "words_per_row": tm.n_words},
             "host_pack_ms": round(pack_ms, 3),
@@ -930,16 +1011,12 @@ def main():
                          "limiter": "latency: one dependent placement chain per candidate (one wave each); the "
                                     "longest chain sets the kernel time, not bytes (DESIGN.md 4)",
                          "chain": chain,
-                         "latency": chain_latency(chain)},
+                         "latency": chain_latency(chain)} if args.full else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sc, nm, cand_off, cand_pods, int(len(nm.spot)), status[:len(loff) - 1],
                                                 nodes_out[:len(lpods)], issued_local, args.cpu_seconds, mutation)
         print(json.dumps(line), flush=True)
-    lib.sr_snapshot_destroy(snap)
-    checker.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -62,6 +62,27 @@ def test_bench_gpus_2_without_a_gpu_fails_loudly():
     assert r.returncode == 2 and "refusing" in r.stderr and r.stdout == ""
 
 
+def test_dump_outputs_writes_float64_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per array (rank r > 0: <name>_rank<r>.npy), integers kept exactly;
+    an array over its share of the byte limit is the same seeded sample, in index order, on every call."""
+    arrays = {"plan_out": np.array([3, -1, 2 ** 40 + 1], np.float64), "status": np.arange(-3, 5, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["plan_out.npy", "status.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    bench.dump_outputs(str(tmp_path / "a"), arrays, rank=2)
+    assert os.path.exists(tmp_path / "a" / "status_rank2.npy")
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 8 * 2 * 100)  # two arrays: 100 elements each
+    big = {"node_of_pod": np.arange(1000, dtype=np.int32), "winner_map": np.arange(7, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    s = np.load(tmp_path / "b" / "node_of_pod.npy")
+    assert s.shape == (100,) and np.all(np.diff(s) > 0) and np.array_equal(s, np.load(tmp_path / "c" / "node_of_pod.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "winner_map.npy"), np.arange(7))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 8 * 2 * 100 + 2 * 128
+
+
 def _fake_kfd(tmp_path, simds):
     base = tmp_path / "kfd_nodes"
     for i, s in enumerate(simds):

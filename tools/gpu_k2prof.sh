@@ -10,7 +10,7 @@ for e in $entries; do
   cfg=${e%%:*}; var=${e#*:}
   name="c${cfg}$([ "$var" = baseline ] || echo "_$var")"
   rm -f "/tmp/k2prof_$name.bin"
-  SR_K2_PROFILE="/tmp/k2prof_$name.bin" timeout -k 10 300 python bench.py --config $cfg --variant $var --steps 3 \
+  SR_K2_PROFILE="/tmp/k2prof_$name.bin" timeout -k 10 300 python bench.py --full --config $cfg --variant $var --steps 3 \
     --warmup 3 --e2e-reps 0 --no-cpu-baseline > "$out/${name}_bench_prof.log" 2>&1 || exit $?
   python tools/k2_profile.py "/tmp/k2prof_$name.bin" > "$out/${name}_k2_wave_profile.txt" 2>&1
   rm -f "/tmp/k2prof_$name.bin"

@@ -23,7 +23,7 @@ for entry in "${B[@]}"; do
   i=$((i+1))
   envs=""; args="$entry"
   if [[ "$entry" == *"|"* ]]; then envs="${entry%%|*}"; args="${entry#*|}"; fi
-  eval "$envs timeout -k 10 400 python bench.py $args" > "$out/bench_$i.log" 2>&1
+  eval "$envs timeout -k 10 400 python bench.py --full $args" > "$out/bench_$i.log" 2>&1
   rc=$?; echo "bench $i ($entry) rc=$rc"; tail -1 "$out/bench_$i.log" | cut -c1-400
   [ $rc -ne 0 ] && exit $rc
 done

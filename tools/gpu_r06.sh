@@ -15,10 +15,10 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit $?
   tail -1 "$out/smoke.log"
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 20 > "$out/bench_c3.log" 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 20 > "$out/bench_c3.log" 2>&1 || exit $?
 tail -1 "$out/bench_c3.log" | cut -c1-400
 SR_BENCH_DEVICE=0 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 50 --warmup 10 --e2e-reps 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 50 --warmup 10 --e2e-reps 2 \
   > "$out/bench_c3_n2_shm.log" 2>&1 || exit $?
 tail -1 "$out/bench_c3_n2_shm.log" | cut -c1-400
 exit 0

@@ -21,7 +21,7 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 for cfg in $cfgs; do
   steps=200; [ "$cfg" = 4 ] && steps=50
-  timeout -k 10 400 python bench.py --config "$cfg" --steps $steps --warmup 10 --cpu-seconds ${CPU_SECONDS:-10} \
+  timeout -k 10 400 python bench.py --full --config "$cfg" --steps $steps --warmup 10 --cpu-seconds ${CPU_SECONDS:-10} \
     > "$out/bench_c$cfg.log" 2>&1
   rc=$?; echo "bench c$cfg rc=$rc"; tail -1 "$out/bench_c$cfg.log" | cut -c1-300
   [ $rc -ne 0 ] && exit $rc

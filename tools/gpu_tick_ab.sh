@@ -13,7 +13,7 @@ for steps in 20 200; do
     for arm in "$@"; do
       i=$((i+1))
       f="$out/s${steps}_arm${i}_rep${rep}.log"
-      env $arm timeout -k 10 200 python bench.py --config $cfg --steps $steps --warmup 20 --no-cpu-baseline \
+      env $arm timeout -k 10 200 python bench.py --full --config $cfg --steps $steps --warmup 20 --no-cpu-baseline \
         --e2e-reps 0 $BENCH_ARGS > "$f" 2>&1 || exit $?
       python - "$f" "$arm" "$steps" <<'PY'
 import json, sys
