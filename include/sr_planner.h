@@ -662,7 +662,9 @@ sr_status sr_comm_init_host(sr_ctx *ctx, int32_t nranks, int32_t rank, sr_allred
  * rank planned it).  `session`: identical on every rank, fresh
  * for the job (it tags the shared words).  Shards must be interleaved:
  * cand_global[i] = (first + i) * nranks + rank (SR_ERR_INVALID_ARG
- * otherwise); max_cand bounds the candidates of one rank's call
+ * otherwise; `first` may differ between the ranks and a rank may plan
+ * nothing: the walk covers the indices some rank planned in the call and
+ * skips the others); max_cand bounds the candidates of one rank's call
  * (SR_ERR_CAPACITY).  Every rank calls it before any rank plans and plans the
  * same sequence of calls; rank 0's sr_destroy removes the name. */
 sr_status sr_comm_init_shm(sr_ctx *ctx, const char *name, uint32_t session, int32_t nranks, int32_t rank,

@@ -201,6 +201,7 @@ struct sr_ctx {
     int32_t base = -1;         // the prepared call's first local candidate (cand_global[0] / nranks), -1: none
     std::string name;
     std::vector<int32_t> act_of;  // scratch: active candidate of each input candidate
+    bool synced = false;       // the current run's walk waited for the stream (shm_wait): its K2 has finished
   } shm;
   sr_allreduce_min_fn host_fn = nullptr;  // sr_comm_init_host: the caller's allreduce(min)
   void* host_user = nullptr;
@@ -334,6 +335,7 @@ sr_status shm_wait(sr_ctx* ctx, F ready, bool own, int32_t r) {
     if (own && !synced && dt > std::chrono::milliseconds(100)) {
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       synced = true;
+      ctx->shm.synced = true;
       if (!ready()) {
         ctx->err = "K2 outcome word not written by this run";
         return SR_ERR_HIP;
@@ -387,10 +389,11 @@ sr_status shm_publish(sr_ctx* ctx, int* par) {
 }
 
 // After K2: the walk in global candidate order over every rank's words (rank
-// g % N holds global index g), up to the first drainable candidate or the
-// first index no rank planned in this call; the result words are written as
-// K3 would (`result`, tagged), the owner's mapping from its K2 (rescheduler.go:
-// 280-286 stops at the first drainable candidate, whichever rank planned it).
+// g % N holds global index g): every index some rank planned in this call, in
+// ascending order, up to the first drainable one -- what allreduce(min) + K3
+// give; the result words are written as K3 would (`result`, tagged), the
+// owner's mapping from its K2 (rescheduler.go:280-286 stops at the first
+// drainable candidate, whichever rank planned it).
 sr_status shm_reduce(sr_ctx* ctx, int p) {
   auto& S = ctx->shm;
   const sr::Workload& w = ctx->cur->wl;
@@ -398,7 +401,7 @@ sr_status shm_reduce(sr_ctx* ctx, int p) {
   const int32_t N = ctx->nranks;
   auto ready = [tag](volatile uint64_t* x) { return static_cast<uint32_t>(*x >> 32) == tag; };
   std::vector<int64_t> n_r(static_cast<size_t>(N)), b_r(static_cast<size_t>(N));
-  int64_t ff = -1, nx = -1, g0 = INT64_MAX;
+  int64_t ff = -1, nx = -1;
   for (int32_t r = 0; r < N; ++r) {
     volatile uint64_t* hd = shm_region(ctx, r, p);
     for (int i : {0, 1, 2, 4}) {
@@ -408,7 +411,6 @@ sr_status shm_reduce(sr_ctx* ctx, int p) {
     std::atomic_thread_fence(std::memory_order_acquire);
     n_r[r] = static_cast<uint32_t>(hd[0]);
     b_r[r] = static_cast<int64_t>(static_cast<uint32_t>(hd[1])) - 1;
-    if (n_r[r] > 0) g0 = std::min(g0, b_r[r] * N + r);
     const int64_t f = static_cast<int64_t>(static_cast<uint32_t>(hd[2])) - 1;
     if (f >= 0) ff = ff < 0 ? f : std::min(ff, f);
     const int64_t x = static_cast<int64_t>(static_cast<uint32_t>(hd[4])) - 1;
@@ -416,12 +418,20 @@ sr_status shm_reduce(sr_ctx* ctx, int p) {
   }
   int64_t first_ok = -1;
   int32_t owner = -1, oci = -1;
-  for (int64_t g = g0; g0 != INT64_MAX; ++g) {
-    const int32_t r = static_cast<int32_t>(g % N);
-    const int64_t li = g / N;
-    if (n_r[r] == 0 || li < b_r[r] || li >= b_r[r] + n_r[r]) break;  // no rank planned g in this call
+  // (the ranks' first local indices may differ: a merge of every rank's
+  // ascending indices, so an index no rank planned in this call is skipped)
+  std::vector<int64_t> at(static_cast<size_t>(N), 0);  // next input candidate of each rank
+  for (;;) {
+    int32_t r = -1;
+    int64_t g = INT64_MAX;
+    for (int32_t q = 0; q < N; ++q) {
+      if (at[q] >= n_r[q]) continue;
+      const int64_t gq = (b_r[q] + at[q]) * N + q;
+      if (gq < g) g = gq, r = q;
+    }
+    if (r < 0) break;  // every planned index walked
     volatile uint64_t* reg = shm_region(ctx, r, p);
-    volatile uint64_t* in = reg + kShmHdr + (li - b_r[r]);
+    volatile uint64_t* in = reg + kShmHdr + at[r]++;
     sr_status st = shm_wait(ctx, [&] { return ready(in); }, false, r);
     if (st != SR_OK) return st;
     const uint32_t v = static_cast<uint32_t>(*in);
@@ -1254,6 +1264,7 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm) {
       if (na) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_node.p, d.out_node, sizeof(int32_t) * na, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(ctx, hipStreamSynchronize(s));
+    ctx->in_flight = false;  // (an earlier winner-only run's K2 has finished too)
   } else if (shm) {
     // (the walk below waits for the outcome words it needs)
   } else {
@@ -1284,8 +1295,16 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm) {
   }
   if (shm) {  // every rank's outcome words in global order (ms_collective: this host walk)
     const auto t0 = std::chrono::steady_clock::now();
+    // a winner-only walk returns at the winner: this rank's K2 may still plan
+    // the candidates after it (res_map in h_early, out_status, out_bytes,
+    // out_cycles), as after finish_early; the next prepare settles before it
+    // moves a buffer.  Not after a wait that synchronised the stream (shm_wait)
+    const bool waited = full || ctx->prof_file;  // synchronised above
+    ctx->shm.synced = false;
+    if (!waited) ctx->in_flight = true;  // (also when the walk fails: another rank's words missing)
     sr_status sst = shm_reduce(ctx, shm_par);
     if (sst != SR_OK) return sst;
+    if (!waited) ctx->in_flight = !ctx->shm.synced;
     if (timing & 4) ctx->t.ms_collective += std::chrono::duration<double, std::milli>(
                                                std::chrono::steady_clock::now() - t0).count();
   }

@@ -121,11 +121,42 @@ class sr_drain_params(ctypes.Structure):
                 ("owner_filter", ctypes.c_int32)]
 
 
-class sr_candidates(ctypes.Structure):
+class _KeepsArrays(ctypes.Structure):
+    """A struct whose pointer fields keep what they were set from.
+
+    ctypes copies only the address out of a pointer object stored into a
+    field, and the pointer `ptr()` returns is the one thing that refers to its
+    numpy array: a struct filled from temporaries, as plan_arrays and most
+    callers fill it, would otherwise leave the library reading and writing
+    arrays the collector is free to take.  The values given to the
+    constructor and assigned to the fields are held per field on the Python
+    object (not in the C layout) until the field is set again or the struct
+    goes."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        for (name, _), value in zip(self._fields_, args):
+            self._hold(name, value)
+        for name, value in kw.items():
+            self._hold(name, value)
+
+    def __setattr__(self, name, value):
+        super().__setattr__(name, value)
+        self._hold(name, value)
+
+    def _hold(self, name, value):
+        held = self.__dict__.setdefault("_held", {})
+        if isinstance(value, ctypes._Pointer) and value:
+            held[name] = value
+        else:  # a plain value, None or a NULL pointer: nothing to keep
+            held.pop(name, None)
+
+
+class sr_candidates(_KeepsArrays):
     _fields_ = [("n_cand", ctypes.c_int32), ("cand_pod_off", P32), ("cand_pods", P32), ("cand_global", P32)]
 
 
-class sr_plan_out(ctypes.Structure):
+class sr_plan_out(_KeepsArrays):
     _fields_ = [("winner", ctypes.c_int32), ("first_ok", ctypes.c_int32), ("first_fallback", ctypes.c_int32),
                 ("winner_npods", ctypes.c_int32), ("checks", ctypes.c_uint64), ("fallback_pods", ctypes.c_uint64),
                 ("status", P32), ("node_of_pod", P32), ("winner_map", P32), ("checks_dense", ctypes.c_uint64)]
@@ -152,7 +183,9 @@ class sr_timing(ctypes.Structure):
 
 
 def ptr(arr, typ):
-    """Pointer to a contiguous numpy array (None for an empty array is fine)."""
+    """Pointer to a contiguous numpy array (None for an empty array is fine).
+    The pointer object refers to the array; a struct field set from it holds
+    the address only, unless the struct keeps its values (_KeepsArrays)."""
     if arr is None:
         return ctypes.cast(None, typ)
     return arr.ctypes.data_as(typ)

@@ -79,3 +79,56 @@ def test_can_drain_node_clears_node_name_of_evaluated_pods_only():
             Pod("c", node_name="od1", containers=[Container(cpu_milli=10)])]
     assert canDrainNode(checker, snap, infos, pods) is not None
     assert [p.node_name for p in pods] == ["", "", "od1"]
+
+
+def test_plan_through_structs_that_alone_hold_their_arrays(checker):
+    """sr_plan_prepare + sr_plan_run on structs built from temporaries: no
+    caller-side reference to any candidate or output array is left, and a
+    collection (and fresh allocations) happen between building the structs and
+    preparing.  The structs keep their arrays (capi.sr_candidates /
+    sr_plan_out), so the library reads the candidates it was given and the
+    results read back through the struct's pointers are the oracle's."""
+    import ctypes
+    import gc
+
+    import numpy as np
+
+    from helpers import Scenario
+    from oracle_lib import oracle_plan
+    from randcluster import rand_scenario
+    from spotplanner import capi
+
+    nodes, spot_pods, cands = rand_scenario(32, n_spot=14, n_cand=20, max_pods=7)
+    flat = [p for c in cands for p in c]
+    sc = Scenario(nodes, spot_pods, flat)
+    lens = [len(c) for c in cands]
+    n, total, maxp = len(cands), sum(lens), max(lens)
+    q0 = sc.q0
+
+    def structs():
+        c = capi.sr_candidates(n, capi.ptr(np.cumsum([0] + lens).astype(np.int32), capi.P32),
+                               capi.ptr(np.arange(q0, q0 + total, dtype=np.int32), capi.P32), None)
+        out = capi.sr_plan_out()
+        out.status = capi.ptr(np.full(n, -99, np.int32), capi.P32)
+        out.node_of_pod = capi.ptr(np.full(max(1, total), -99, np.int32), capi.P32)
+        out.winner_map = capi.ptr(np.full(max(1, maxp), -99, np.int32), capi.P32)
+        return c, out
+
+    c, out = structs()
+    gc.collect()
+    churn = [np.full(k, -7, np.int32) for k in (n + 1, total, n, max(1, total), max(1, maxp)) for _ in range(8)]
+    lib = capi.load_planner()
+    h = sc.product_snapshot()
+    try:
+        assert lib.sr_plan_prepare(checker.handle, h, sc.ptr, ctypes.byref(c)) == capi.SR_OK, checker.last_error()
+        gc.collect()
+        assert lib.sr_plan_run(checker.handle, ctypes.byref(out)) == capi.SR_OK, checker.last_error()
+    finally:
+        lib.sr_snapshot_destroy(h)
+    assert all(int(a[0]) == -7 and int(a[-1]) == -7 for a in churn)  # nothing wrote into the new allocations
+    cand_off = np.cumsum([0] + lens).astype(np.int32)
+    o = oracle_plan(sc.oracle_snapshot(), sc.ptr, cand_off, np.arange(q0, q0 + total, dtype=np.int32), mode=1)
+    assert [out.status[i] for i in range(n)] == [int(s) for s in o["status"]]
+    assert [out.node_of_pod[i] for i in range(total)] == [int(x) for x in o["node_of_pod"]]
+    assert (out.first_ok, out.first_fallback, out.winner) == (o["first_ok"], o["first_fallback"], o["winner"])
+    assert [out.winner_map[i] for i in range(out.winner_npods)] == [int(x) for x in o["winner_map"]]
