@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SR_ABI_VERSION 9
+#define SR_ABI_VERSION 10
 
 /* ------------------------------------------------------------------ status */
 typedef int32_t sr_status;
@@ -94,7 +94,8 @@ typedef int32_t sr_status;
 #define SR_CAND_FALLBACK  (-2)  /* outside the encoded predicate set: evaluate with the reference path */
 #define SR_CAND_EMPTY     (-3)  /* no pods to move: run() skips it (rescheduler.go:260-264) */
 #define SR_CAND_SKIPPED   (-4)  /* sr_plan_first: after the first drainable candidate, never evaluated
-                                   (run() drains it and breaks, rescheduler.go:280-286) */
+                                   (run() drains it and breaks, rescheduler.go:280-286); sr_plan_sequence:
+                                   below first_cand, or after the pass stopped */
 
 /* ------------------------------------------------------------- cluster model */
 /* Nodes (k8s.io/api/core/v1 Node), in the order the node lister returned them
@@ -510,7 +511,8 @@ const char *sr_build_info(void);
  * library would otherwise read fields past the end of a shorter struct (ABI 5
  * added sr_cluster.volumes and pod_stamp; ABI 6 the sr_timing enc_reused /
  * enc_pod_patches counters, which sr_get_timing writes; ABI 7 sr_timing.ms_collective; ABI 8
- * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields). */
+ * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields; ABI 10
+ * sr_plan_sequence). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -580,6 +582,49 @@ sr_status sr_plan(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluste
  * on some rank (the reduced smallest unplanned index lies above it). */
 sr_status sr_plan_first(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluster,
                         const sr_candidates *cands, sr_plan_out *out);
+
+/* Several consistent drains in one tick: an extension beyond the reference,
+ * which drains one node per tick and sleeps nodeDrainDelay.  The pass is the
+ * loop of run() (rescheduler.go:228-287) with the `break` at :286 replaced by
+ * "keep the forked state and go on", up to a budget:
+ *
+ *   for c in candidates[first_cand:], in NodeInfoArray order:
+ *     no pods: SR_CAND_EMPTY, continue                        (:260-264)
+ *     outside the encoded predicate set: stop at c (SR_SEQ_FALLBACK)
+ *     Fork; err = canDrainNode(c)
+ *     err: Revert; status[c] = failing pod; continue          (:271-275)
+ *     keep the added pods (:366); drained.append(c)
+ *     len(drained) == max_drains: stop (SR_SEQ_BUDGET)
+ *   stop (SR_SEQ_END)
+ *
+ * A failed candidate is not looked at again in the pass.  Afterwards `snap`
+ * holds every drained candidate's pods on their planned nodes (what the Go
+ * snapshot holds after canDrainNode returns nil).  With max_drains = 1 and
+ * first_cand = 0 the result is sr_plan_first's.  The device plans in rounds:
+ * every candidate above the last drain from the current snapshot, the first
+ * drainable one is the next drain.  Single GPU: SR_ERR_STATE
+ * with a communicator attached or a forked snapshot; SR_ERR_INVALID_ARG for
+ * cand_global != NULL, max_drains < 1 or first_cand out of range.  On an error
+ * after some commits, n_drained / drained say what `snap` already holds. */
+#define SR_SEQ_END      0  /* every candidate from first_cand on was judged */
+#define SR_SEQ_BUDGET   1  /* max_drains reached; later candidates SR_CAND_SKIPPED */
+#define SR_SEQ_FALLBACK 2  /* the pass reached a fallback candidate (stop_cand): the shim judges it
+                              with the reference path and calls again with first_cand = stop_cand + 1 */
+typedef struct {
+  int32_t  max_drains;    /* in, >= 1 */
+  int32_t  first_cand;    /* in, 0 <= first_cand <= n_cand; candidates below it: SR_CAND_SKIPPED */
+  int32_t  n_drained, stop, stop_cand;   /* out; stop_cand: the fallback candidate, else -1 */
+  int32_t  rounds;        /* out: device rounds (prepare + K2), <= n_drained + 1 */
+  int32_t  rounds_k0;     /* out: ... of which launched K0 */
+  int32_t  rounds_reused; /* out: ... of which kept the candidate side (sr_timing.enc_reused) */
+  int32_t *drained;       /* [min(max_drains, n_cand)] out, drain order (ascending) */
+  int32_t *status;        /* [n_cand] optional: SR_CAND_OK drained, >= 0 failing pod as judged in the
+                             pass, EMPTY, FALLBACK (stop_cand only), SKIPPED (not judged) */
+  int32_t *node_of_pod;   /* [pods of the list] optional: every judged candidate's canDrainNode
+                             mapping (pods before a failing pod included), -1 elsewhere */
+} sr_sequence_out;
+sr_status sr_plan_sequence(sr_ctx *ctx, sr_snapshot *snap /* modified */, const sr_cluster *cluster,
+                           const sr_candidates *cands, sr_sequence_out *out);
 
 /* Split form of sr_plan for a resident workload (bench): prepare = host
  * encoding + upload; run = device-only tick over the resident buffers

@@ -456,6 +456,29 @@ __device__ __forceinline__ void write_winner(const DevWorkload& w) {
 // K3: one wave (after the collective on multi-GPU runs).
 __global__ __launch_bounds__(64) void k3_winner(DevWorkload w) { write_winner(w); }
 
+// K3 of a sequence round (sr_plan_sequence): the ledger.  The candidates the
+// round judged -- global index above the floor, up to the round's first
+// drainable candidate (d_min[0]) or to just before the first fallback above
+// the floor -- keep their K2 outcome in the sequence's own arrays, indexed as
+// the caller's list; the next round's K2 then overwrites out_status / out_node
+// freely.  One thread per active candidate (the active candidates ascend in
+// global index, so the judged ones are neighbours).
+__global__ __launch_bounds__(256) void k3_sequence(SeqRound r) {
+  const unsigned long long ok = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(r.d_min),
+                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int win = ok == ~0ull ? INT_MAX : static_cast<int>(ok >> 32);
+  const int end = win < r.fb_stop ? win : r.fb_stop - 1;
+  for (int ci = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x); ci < r.n_cand;
+       ci += static_cast<int>(gridDim.x * blockDim.x)) {
+    const int g = r.cand_global[ci];
+    if (g <= r.floor || g > end) continue;
+    r.seq_status[g] = r.out_status[ci];
+    const int o = r.cand_off[ci], np = r.cand_off[ci + 1] - o;
+    const int dst = r.in_off[g] - r.in_off[0];
+    for (int k = 0; k < np; ++k) r.seq_node[dst + k] = r.out_node[o + k];
+  }
+}
+
 // The bits a pod conflicts with, from the state bits it sets: anti-affinity
 // pairs (A: has the term, B: selected by it) swapped, host-port bits as they
 // are (encode.cpp / antiaff.cpp).  An involution.
@@ -2532,19 +2555,33 @@ __device__ __forceinline__ K2Entry k2_entry(const DevWorkload& w, const int4* __
 
 // A K2 wave's outcome: status, bytes, the packed first-drainable minimum, the
 // profile record and (single rank) the tagged words the host polls.
+// Once per run, by lane 0 of candidate 0's wave (whether or not it plans the
+// candidate): the next run's first d_min word (K0 may not run then), this run's others.
+__device__ __forceinline__ void k2_once(const DevWorkload& w) {
+  unsigned long long* dn = reinterpret_cast<unsigned long long*>(w.d_min_next);
+  unsigned long long* dm = reinterpret_cast<unsigned long long*>(w.d_min);
+  dn[0] = ~0ull;
+  dm[1] = w.first_fallback_local < 0 ? ~0ull : static_cast<unsigned long long>(w.first_fallback_local) << 32;
+  dm[2] = w.rank_next;
+}
+
+// A sequence round's entries at or below the floor (DevWorkload::cand_floor):
+// judged in an earlier round.  The wave plans nothing, never enters d_min and
+// writes neither out_status, out_node nor a result word; candidate 0's wave
+// keeps the once-per-run duty, and a recorded duration is zero.
+__device__ __forceinline__ void k2_skipped(const DevWorkload& w, int ci) {
+  if ((threadIdx.x & 63) != 0) return;
+  if (ci == 0) k2_once(w);
+  if (w.out_cycles) w.out_cycles[ci] = 0;
+}
+
 template <bool PROF>
 __device__ __forceinline__ void k2_finish(const DevWorkload& w, const K2Entry& x, int status, int wide,
                                           uint32_t nbytes, const K2Stats& st) {
   const int lane = threadIdx.x & 63;
   const int ci = x.ci, p0 = x.p0, np = x.np;
   int best = 0;  // lane 0: this candidate is the first drainable one so far
-  if (lane == 0 && ci == 0) {  // once per run: the next run's first word (K0 may not run then), this run's others
-    unsigned long long* dn = reinterpret_cast<unsigned long long*>(w.d_min_next);
-    unsigned long long* dm = reinterpret_cast<unsigned long long*>(w.d_min);
-    dn[0] = ~0ull;
-    dm[1] = w.first_fallback_local < 0 ? ~0ull : static_cast<unsigned long long>(w.first_fallback_local) << 32;
-    dm[2] = w.rank_next;
-  }
+  if (lane == 0 && ci == 0) k2_once(w);
   if (lane == 0) {
     w.out_status[ci] = status;
     w.out_bytes[ci] = nbytes;
@@ -2608,6 +2645,10 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   const int li = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * (blockDim.x >> 6)) + wave);
   if (li >= n_list) return;
   const K2Entry x = k2_entry<PROF>(w, list, li);
+  if (x.g <= w.cand_floor) {  // (a sequence round: judged before)
+    k2_skipped(w, x.ci);
+    return;
+  }
   const int ci = x.ci, p0 = x.p0, np = x.np;
   K2Lds& L = *reinterpret_cast<K2Lds*>(k2_lds + static_cast<size_t>(wave) * (sizeof(K2Lds) / 8));
 
@@ -2675,6 +2716,17 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
   if constexpr (!XT) {
     static_assert(sizeof(CoopArea) <= (kCoopWaves - 1) * 64 * kNHS * 8, "the cooperative area fits the helpers' LDS");
     if (static_cast<int>(blockIdx.x) < nco) {
+      // a sequence round: every wave of the block reads the block's entry and
+      // decides alike, before the first barrier, whether the block plans it --
+      // no helper waits for a chain that never starts
+      if (w.cand_floor >= 0) {
+        const int bi = static_cast<int>(blockIdx.x);
+        const int4 e = bi < w.n_list_head ? w.list_head[bi] : list[bi];
+        if (__builtin_amdgcn_readfirstlane(e.w) <= w.cand_floor) {
+          if (wave == 0) k2_skipped(w, __builtin_amdgcn_readfirstlane(e.x));
+          return;
+        }
+      }
       CoopArea* A = reinterpret_cast<CoopArea*>(k2_lds + region);
       if (wave != 0) {
         coop_helper(w, *A, wave);
@@ -2702,6 +2754,10 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
   int4 xe = {-1, -1, -1, 0};
   if (XT) xe = w.list_ext[li];  // issued with the entry: one round trip for both
   const K2Entry x = k2_entry<PROF>(w, list, li);
+  if (x.g <= w.cand_floor) {  // (a sequence round: judged before)
+    k2_skipped(w, x.ci);
+    return;
+  }
   uint64_t* F = k2_lds + static_cast<size_t>(wave) * region;
   K2Stats st;
   int status = -1;
@@ -2877,6 +2933,13 @@ hipError_t launch_placement(const DevWorkload& w, hipStream_t s, hipEvent_t ev0,
 
 hipError_t launch_winner(const DevWorkload& w, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   launch(k3_winner, dim3(1), dim3(64), 0, s, ev0, ev1, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_sequence(const SeqRound& r, hipStream_t s) {
+  if (r.n_cand <= 0) return hipSuccess;
+  const unsigned blocks = static_cast<unsigned>(std::min(64, (r.n_cand + 255) / 256));
+  hipLaunchKernelGGL(k3_sequence, dim3(blocks), dim3(256), 0, s, r);
   return hipGetLastError();
 }
 #endif  // SR_KPART 0

@@ -117,6 +117,8 @@ struct DevWorkload {
   int32_t k2_excl;     // node order: exclusive candidates placed with the taken-mask step (SR_K2_EXCL=0: never)
   int32_t n_coop;      // node-order kernel, four waves per block: the first n_coop work-list entries (the costliest)
                        // are planned by one block each, its other waves scanning far resolutions with the chain
+  int32_t cand_floor;  // sr_plan_sequence rounds: a K2 wave whose entry's global index is <= cand_floor plans
+                       // nothing and writes no outcome (judged in an earlier round); -1: every entry is planned
   int32_t k2_mode;     // 0: node-order first fit where it applies (<= 64 pods, <= 64-word rows);
                        // 1: pod order everywhere (SR_K2_MODE=1, A/B measurement)
   uint64_t* prof;      // optional [n_cand][16] K2 + [kK0ProfWaves][2] K0 per-wave profile
@@ -137,5 +139,26 @@ hipError_t launch_placement(const DevWorkload& w, hipStream_t s, hipEvent_t ev0 
 // K3: winner mapping into `result` (after the collective when ranks > 1), then the run's seq.
 // Not launched when K2 writes res_stat / res_map itself (single rank).
 hipError_t launch_winner(const DevWorkload& w, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// One round of sr_plan_sequence for the ledger kernel: the
+// candidates judged in the round are the active ones with a global index in
+// (floor, min(first drainable, fb_stop - 1)], the first drainable one read from
+// d_min[0] after K2.
+struct SeqRound {
+  const int32_t* d_min;        // the round's d_min (K2's atomicMin of the first drainable candidate)
+  const int32_t* cand_global;  // [n_cand] the active candidates' indices in the caller's list
+  const int32_t* cand_off;     // [n_cand + 1] their first active pod
+  const int32_t* out_status;   // [n_cand] K2's outcomes (the next round's K2 overwrites them)
+  const int32_t* out_node;     // [active pods]
+  const int32_t* in_off;       // [candidates of the caller's list + 1] the caller's cand_pod_off
+  int32_t n_cand;
+  int32_t floor;               // the round's DevWorkload::cand_floor
+  int32_t fb_stop;             // first fallback candidate above the floor (INT32_MAX: none)
+  int32_t* seq_status;         // [candidates of the caller's list] the sequence's ledger, by the caller's indices
+  int32_t* seq_node;           // [pods of the caller's list]
+};
+// K3 of a sequence round: copies the judged candidates' out_status / out_node
+// into the ledger (after K2 in stream order; no host synchronisation).
+hipError_t launch_sequence(const SeqRound& r, hipStream_t s);
 
 }  // namespace sr

@@ -165,6 +165,11 @@ struct sr_ctx {
   // the general kernel's dispatch
   int32_t k2_dispatch_events = 1;
   DevBuf out_cycles;
+  // sr_plan_sequence: the ledger of what each round decided (by the caller's
+  // candidate and pod indices; K3 of a round fills it, one copy brings it down
+  // at the end of the sequence) and the caller's cand_pod_off on the device
+  DevBuf seq_status, seq_node, seq_off;
+  HostBuf h_seq_status, h_seq_node, h_seq_off;
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   uint64_t run_count = 0;      // runs of this context: d_min alternates between two buffers
@@ -899,6 +904,7 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   d.out_status = static_cast<int32_t*>(ctx->out_status.p);
   d.out_bytes = static_cast<uint32_t*>(ctx->out_bytes.p);
   d.d_min = static_cast<int32_t*>(ctx->dmin.p);
+  d.cand_floor = -1;  // a sequence round sets its own
   d.k2_mode = ctx->k2_mode;
   d.k2_narrow = ctx->k2_narrow;
   d.k2_wpb = ctx->k2_wpb;
@@ -1074,7 +1080,87 @@ sr_status finish_early(sr_ctx* ctx, sr_plan_out* out) {
   return SR_OK;
 }
 
-sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm) {
+// One round of sr_plan_sequence, host side.
+struct SeqWalk {
+  int32_t floor = -1;     // in: the cursor (candidates at or below it were judged in earlier rounds)
+  int32_t winner = -1;    // out: the round's first drainable candidate, in the caller's indices
+  int32_t fallback = -1;  // out: the fallback candidate the walk stopped at
+  int32_t end = -1;       // out: the last candidate the walk judged (below the fallback it stopped at)
+  std::vector<int32_t> map;  // out: the winner's mapping
+};
+
+// The first fallback candidate above the floor (INT32_MAX: none).
+int32_t first_fallback_above(const sr::Workload& w, int32_t floor) {
+  for (int32_t i = floor + 1; i < w.n_input_cand; ++i)
+    if (w.status_host[i] == SR_CAND_FALLBACK) return i;
+  return INT32_MAX;
+}
+
+// The end of a sequence round: as finish_early, but the walk over K2's
+// per-candidate words starts above the floor (the skipped candidates' waves
+// store no word and may be scheduled last: the work list is in cost order)
+// and takes the host-decided candidates in between (no pods: passed over; the
+// reference path: the walk stops there).
+sr_status finish_sequence(sr_ctx* ctx, SeqWalk* sq) {
+  const sr::Workload& w = ctx->cur->wl;
+  const sr::DevWorkload& d = ctx->dw;
+  if (ctx->timing_cur) ctx->t.n_runs += 1;
+  volatile uint64_t* stat = static_cast<volatile uint64_t*>(ctx->h_early.p);
+  volatile uint64_t* map = stat + d.n_cand;
+  const uint32_t tag = d.seq;
+  auto ready = [&](volatile uint64_t* p) { return static_cast<uint32_t>(*p >> 32) == tag; };
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t spins = 0;
+  bool synced = false;
+  auto wait = [&](volatile uint64_t* p) -> sr_status {
+    while (!ready(p)) {
+      if (!synced && (++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        synced = true;
+      }
+      if (synced && !ready(p)) {
+        ctx->err = "K2 result word not written by this run";
+        return SR_ERR_HIP;
+      }
+    }
+    return SR_OK;
+  };
+  ctx->in_flight = d.n_list > 0;  // (also when the walk fails)
+  sq->winner = sq->fallback = -1;
+  sq->end = w.n_input_cand - 1;
+  // the active candidates ascend in the caller's index (cand_src): k follows i
+  int32_t k = static_cast<int32_t>(std::upper_bound(w.cand_src.begin(), w.cand_src.end(), sq->floor) -
+                                   w.cand_src.begin());
+  for (int32_t i = sq->floor + 1; i < w.n_input_cand; ++i) {
+    if (k < d.n_cand && w.cand_src[k] == i) {
+      sr_status st = wait(stat + k);
+      if (st != SR_OK) return st;
+      if (static_cast<uint32_t>(stat[k]) == 1) {
+        sq->winner = sq->end = i;
+        break;
+      }
+      ++k;
+    } else if (w.status_host[i] == SR_CAND_FALLBACK) {
+      sq->fallback = i;
+      sq->end = i - 1;
+      break;
+    }
+  }
+  if (sq->winner >= 0) {
+    const int32_t o = w.cand_off[k], np = w.cand_off[k + 1] - o;
+    for (int32_t q = 0; q < np; ++q) {
+      sr_status st = wait(map + o + q);
+      if (st != SR_OK) return st;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    sq->map.resize(static_cast<size_t>(np));
+    for (int32_t q = 0; q < np; ++q) sq->map[q] = static_cast<int32_t>(static_cast<uint32_t>(map[o + q]));
+  }
+  if (synced) ctx->in_flight = false;
+  return SR_OK;
+}
+
+sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* sq = nullptr) {
   if (!ctx->prepared) {
     ctx->err = "sr_plan_run before sr_plan_prepare";
     return SR_ERR_STATE;
@@ -1086,7 +1172,7 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm) {
   const bool collective = has_comm(ctx) && use_comm;
   // Single rank, winner only: K2 writes each candidate's outcome to the host
   // and the run returns once the candidates up to the winner are known (no K3)
-  const bool early = !collective && !full && !ctx->prof_file;
+  const bool early = !collective && !full && (!ctx->prof_file || sq);
   const int32_t timing = (ctx->timing_runs++ % ctx->timing_every) == 0 ? ctx->timing : 0;
   ctx->timing_cur = timing;
   do ctx->seq = g_run_seq.fetch_add(1, std::memory_order_relaxed) + 1;
@@ -1236,6 +1322,22 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm) {
                                 hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipEventRecord(slc.ev_cost, s));
     slc.cost_gen = w.cand_gen;
+  }
+  if (sq) {  // a sequence round: the ledger after K2 (after the join of a split launch), then the walk
+    sr::SeqRound r{};
+    r.d_min = d.d_min;
+    r.cand_global = d.cand_global;
+    r.cand_off = d.cand_off;
+    r.out_status = d.out_status;
+    r.out_node = d.out_node;
+    r.in_off = static_cast<const int32_t*>(ctx->seq_off.p);
+    r.n_cand = d.n_cand;
+    r.floor = sq->floor;
+    r.fb_stop = first_fallback_above(w, sq->floor);
+    r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
+    r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
+    HIP_TRY(ctx, sr::launch_sequence(r, s));
+    return finish_sequence(ctx, sq);
   }
   if (early) return finish_early(ctx, out);
   if (!shm) {  // the shared-memory transport has no collective and no K3 (shm_reduce below)
@@ -1426,7 +1528,7 @@ void sr_destroy(sr_ctx* ctx) {
     if (ctx->rank == 0) shm_unlink(ctx->shm.name.c_str());  // the ranks keep their mappings
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
-                    &ctx->scratch})
+                    &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1434,7 +1536,8 @@ void sr_destroy(sr_ctx* ctx) {
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->out_cycles.p) (void)hipFree(ctx->out_cycles.p);
-  for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm})
+  for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm,
+                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off})
     if (b->p) (void)hipHostFree(b->p);
   for (auto& sl : ctx->slots) {
     if (sl->arena.p) (void)hipFree(sl->arena.p);
@@ -1559,6 +1662,136 @@ static sr_status plan_first(sr_ctx* ctx, const sr_snapshot* snap, const sr_clust
   out->winner = (out->first_ok >= 0 && (out->first_fallback < 0 || out->first_fallback > out->first_ok))
                     ? out->first_ok : -1;
   ctx->t.prefix_batches = batches;
+  return SR_OK;
+}
+
+// Several consistent drains in one tick: rounds over the whole
+// candidate list -- the same cand_pod_off / cand_pods / stamps every round, so
+// the encoder's candidate-side reuse applies and a round's prepare re-encodes
+// the spot nodes the last commit touched.  A round plans every candidate above
+// the cursor from the current snapshot (K2 skips the others: cand_floor); its
+// first drainable candidate is the next drain, the candidates between the
+// cursor and it failed against the state the serial pass would have shown them.
+sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                           sr_sequence_out* out) {
+  if (!ctx || !snap || !cluster || !cands || !out || cands->n_cand < 0) return SR_ERR_INVALID_ARG;
+  const int32_t n = cands->n_cand;
+  out->n_drained = out->rounds = out->rounds_k0 = out->rounds_reused = 0;
+  out->stop = SR_SEQ_END;
+  out->stop_cand = -1;
+  if (cands->cand_global) {
+    ctx->err = "sr_plan_sequence plans one GPU's whole candidate list: cand_global must be NULL";
+    return SR_ERR_INVALID_ARG;
+  }
+  if (out->max_drains < 1 || out->first_cand < 0 || out->first_cand > n || (n > 0 && !out->drained)) {
+    ctx->err = "sr_plan_sequence: max_drains < 1, first_cand out of range or no drained array";
+    return SR_ERR_INVALID_ARG;
+  }
+  if (has_comm(ctx)) {
+    ctx->err = "sr_plan_sequence with a communicator attached (single GPU only)";
+    return SR_ERR_STATE;
+  }
+  if (snap->forked) {
+    ctx->err = "sr_plan_sequence on a forked snapshot";
+    return SR_ERR_STATE;
+  }
+  const int32_t* off = cands->cand_pod_off;
+  const int32_t n_pods = n > 0 ? off[n] - off[0] : 0;
+  const bool want = out->status != nullptr || out->node_of_pod != nullptr;
+  // what the host knows of each candidate: 0 not judged, 1 judged on the device (the ledger), 2 no pods, 3 fallback
+  std::vector<uint8_t> how(static_cast<size_t>(n), 0);
+  int32_t cursor = out->first_cand - 1;
+  bool ledger = false;  // the device arrays are sized and cand_pod_off is up
+  SeqWalk sq;
+  for (;;) {
+    // candidates without pods need no round (rescheduler.go:260-264); no round when nothing else is left
+    int32_t next = cursor + 1;
+    while (next < n && off[next + 1] == off[next]) how[next++] = 2;
+    if (next >= n) break;  // SR_SEQ_END
+    sr_status st = prepare(ctx, snap, cluster, cands);
+    if (st != SR_OK) return st;
+    const sr::Workload& w = ctx->cur->wl;
+    sq.floor = cursor;
+    const bool any_active = !w.cand_src.empty() && w.cand_src.back() > cursor;
+    if (any_active) {
+      if (!ledger) {  // (after prepare's settle: no earlier kernel reads them)
+        HIP_TRY(ctx, dev_reserve(ctx->seq_status, sizeof(int32_t) * static_cast<size_t>(n)));
+        HIP_TRY(ctx, dev_reserve(ctx->seq_node, sizeof(int32_t) * static_cast<size_t>(std::max(1, n_pods))));
+        HIP_TRY(ctx, dev_reserve(ctx->seq_off, sizeof(int32_t) * (static_cast<size_t>(n) + 1)));
+        HIP_TRY(ctx, host_reserve(ctx->h_seq_off, sizeof(int32_t) * (static_cast<size_t>(n) + 1)));
+        std::memcpy(ctx->h_seq_off.p, off, sizeof(int32_t) * (static_cast<size_t>(n) + 1));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_off.p, ctx->h_seq_off.p, sizeof(int32_t) * (static_cast<size_t>(n) + 1),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        ledger = true;
+      }
+      ctx->dw.cand_floor = cursor;
+      ctx->dw.prof = nullptr;  // (SR_K2_PROFILE records whole runs)
+      sr_plan_out o{};
+      st = run(ctx, &o, false, false, &sq);
+      ctx->dw.cand_floor = -1;  // (the launches hold their copy: a later sr_plan_run of this workload plans everything)
+      if (st != SR_OK) return st;
+      out->rounds += 1;
+      out->rounds_k0 += ctx->dw.k0_skip ? 0 : 1;
+      out->rounds_reused += ctx->t.enc_reused ? 1 : 0;
+    } else {  // every candidate above the cursor is decided by the host
+      sq.winner = sq.fallback = -1;
+      sq.end = n - 1;
+      const int32_t fb = first_fallback_above(w, cursor);
+      if (fb != INT32_MAX) sq.fallback = fb, sq.end = fb - 1;
+    }
+    for (int32_t i = cursor + 1; i <= sq.end; ++i) how[i] = w.status_host[i] == SR_CAND_EMPTY ? 2 : 1;
+    if (sq.winner < 0) {
+      if (sq.fallback >= 0) {
+        how[sq.fallback] = 3;
+        out->stop = SR_SEQ_FALLBACK;
+        out->stop_cand = sq.fallback;
+      }
+      break;
+    }
+    // the commit: the winner's pods stay on their planned nodes (rescheduler.go:366)
+    const int32_t c = sq.winner, np = off[c + 1] - off[c];
+    if (static_cast<int32_t>(sq.map.size()) != np) {
+      ctx->err = "sr_plan_sequence: the winner's mapping does not cover its pods";
+      return SR_ERR_HIP;
+    }
+    for (int32_t q = 0; q < np; ++q) {
+      if (sq.map[q] < 0 || sq.map[q] >= sr_snapshot_num_nodes(snap)) {
+        ctx->err = "sr_plan_sequence: the winner's mapping names no spot node";
+        return SR_ERR_HIP;
+      }
+    }
+    for (int32_t q = 0; q < np; ++q) sr::snapshot_add_pod(snap, cluster, cands->cand_pods[off[c] + q], sq.map[q]);
+    out->drained[out->n_drained++] = c;
+    cursor = c;
+    if (out->n_drained == out->max_drains) {
+      out->stop = SR_SEQ_BUDGET;
+      break;
+    }
+  }
+  if (want) {
+    const int32_t* hs = nullptr;
+    const int32_t* hn = nullptr;
+    if (ledger) {  // the one copy of the sequence (waits for the last round's K2 and ledger kernel)
+      HIP_TRY(ctx, host_reserve(ctx->h_seq_status, sizeof(int32_t) * static_cast<size_t>(n)));
+      HIP_TRY(ctx, host_reserve(ctx->h_seq_node, sizeof(int32_t) * static_cast<size_t>(std::max(1, n_pods))));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_seq_status.p, ctx->seq_status.p, sizeof(int32_t) * static_cast<size_t>(n),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+      if (n_pods > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_seq_node.p, ctx->seq_node.p, sizeof(int32_t) * static_cast<size_t>(n_pods),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      ctx->in_flight = false;
+      hs = static_cast<const int32_t*>(ctx->h_seq_status.p);
+      hn = static_cast<const int32_t*>(ctx->h_seq_node.p);
+    }
+    for (int32_t i = 0; i < n; ++i) {
+      const bool dev = how[i] == 1;
+      if (out->status)
+        out->status[i] = dev ? hs[i] : how[i] == 2 ? SR_CAND_EMPTY : how[i] == 3 ? SR_CAND_FALLBACK : SR_CAND_SKIPPED;
+      if (out->node_of_pod)
+        for (int32_t q = off[i] - off[0]; q < off[i + 1] - off[0]; ++q) out->node_of_pod[q] = dev ? hn[q] : -1;
+    }
+  }
   return SR_OK;
 }
 

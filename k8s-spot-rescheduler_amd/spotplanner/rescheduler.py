@@ -3,6 +3,8 @@
 findSpotNodeForPod (rescheduler.go:338-353), canDrainNode (:357-370),
 validateArgs (:407-417), podID (:402-404), and plan_arrays: the planning
 segment of run() (:228-287) evaluated for every candidate at once on the GPU.
+plan_sequence_arrays / drainSequence go beyond the reference, which drains one
+node per tick: several consistent drains planned in one tick (sr_plan_sequence).
 """
 from __future__ import annotations
 
@@ -200,3 +202,71 @@ def plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr
         raise PlannerError("sr_plan: %d %s" % (st, predicateChecker.last_error()))
     return PlanResult(o.winner, o.first_ok, o.first_fallback, status[:n], nodes[: int(cand_off[-1]) if n else 0],
                       wmap[: o.winner_npods], int(o.checks), int(o.fallback_pods))
+
+
+@dataclass
+class SequenceResult:
+    drained: np.ndarray      # candidates to drain, in drain order (ascending)
+    stop: int                # capi.SR_SEQ_END / SR_SEQ_BUDGET / SR_SEQ_FALLBACK
+    stop_cand: int           # the fallback candidate the pass stopped at, else -1
+    status: np.ndarray       # per candidate: SR_CAND_* or failing pod index, as judged in the pass
+    node_of_pod: np.ndarray  # flat, spot position per candidate pod (-1 not placed / not judged)
+    rounds: int              # device rounds; of which launched K0 / kept the candidate side
+    rounds_k0: int
+    rounds_reused: int
+
+
+def plan_sequence_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
+                         cand_pods: np.ndarray, max_drains: Optional[int] = None, first_cand: int = 0,
+                         full: bool = True) -> SequenceResult:
+    """sr_plan_sequence over caller-built arrays: the loop of rescheduler.go:228-287 with
+    the `break` at :286 replaced by "keep the forked state and go on", up to max_drains
+    (None: no budget).  The snapshot is modified: afterwards it holds every drained
+    candidate's pods on their planned nodes."""
+    lib = predicateChecker.lib
+    n = len(cand_off) - 1
+    budget = 2 ** 31 - 1 if max_drains is None else int(max_drains)  # None: no budget (the pass ends with SR_SEQ_END)
+    c = capi.sr_candidates(n, capi.ptr(cand_off, capi.P32), capi.ptr(cand_pods, capi.P32), None)
+    n_pods = int(cand_off[-1] - cand_off[0]) if n > 0 else 0
+    drained = np.full(max(min(max(budget, 1), max(n, 1)), 1), -1, np.int32)
+    status = np.full(max(n, 1), capi.SR_CAND_SKIPPED, np.int32)
+    nodes = np.full(max(n_pods, 1), -1, np.int32)
+    o = capi.sr_sequence_out()
+    o.max_drains = budget
+    o.first_cand = int(first_cand)
+    o.drained = capi.ptr(drained, capi.P32)
+    o.status = capi.ptr(status, capi.P32) if full else None
+    o.node_of_pod = capi.ptr(nodes, capi.P32) if full else None
+    st = lib.sr_plan_sequence(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c), ctypes.byref(o))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_plan_sequence: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        err.drained = drained[: o.n_drained].copy()  # what the snapshot already holds
+        raise err
+    return SequenceResult(drained[: o.n_drained].copy(), o.stop, o.stop_cand, status[:n], nodes[:n_pods],
+                          o.rounds, o.rounds_k0, o.rounds_reused)
+
+
+def drainSequence(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                  candidates: Sequence[Sequence[Pod]], max_drains: Optional[int] = None, first_cand: int = 0):
+    """Several consistent drains in one tick, in the style of canDrainNode: `candidates`
+    are the podsForDeletion lists of the on-demand nodes in NodeInfoArray order.  Returns
+    (SequenceResult, plans) with plans = [(candidate index, [spot node name per pod])] in
+    drain order; the snapshot keeps the drained candidates' pods.  On SR_SEQ_FALLBACK the
+    caller judges candidate `stop_cand` with the reference path and calls again with
+    first_cand = stop_cand + 1."""
+    _check_order(spotSnapshot, nodes)
+    flat = [p for c in candidates for p in c]
+    enc = spotSnapshot.encode_pods(flat)
+    cand_off = np.zeros(len(candidates) + 1, np.int32)
+    cand_off[1:] = np.cumsum([len(c) for c in candidates])
+    cand_pods = np.arange(len(flat), dtype=np.int32)
+    r = plan_sequence_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off, cand_pods, max_drains,
+                             first_cand)
+    plans = []
+    for c in r.drained:
+        seg = r.node_of_pod[cand_off[c]:cand_off[c + 1]]
+        for p in candidates[int(c)]:
+            p.node_name = ""  # :341
+        plans.append((int(c), [nodes[int(k)].Node.name for k in seg]))
+    return r, plans
