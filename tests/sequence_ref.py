@@ -10,6 +10,7 @@ holds after canDrainNode returns nil) and the pass goes on from that state.
 from __future__ import annotations
 
 import ctypes
+import zlib
 from dataclasses import dataclass, field
 from typing import Callable, Dict, Optional
 
@@ -18,8 +19,10 @@ import numpy as np
 from helpers import Scenario
 from oracle_lib import OracleSnapshot, load_oracle, oracle_plan
 from randcluster import rand_scenario
+from scenario_gen import init_and_gpu_scenario, rand_spread_replicas, rand_spread_scenario, rand_volume_scenario
 from spotplanner import capi
-from spotplanner.synth import AFFINITY, SynthCluster, build_candidates, new_node_map
+from spotplanner.model import Container, Node, PersistentVolume, PersistentVolumeClaim, Pod, Volume, VolumeWorld
+from spotplanner.synth import AFFINITY, REALISTIC, SynthCluster, build_candidates, new_node_map
 
 OK, FB, EMPTY, SKIPPED = capi.SR_CAND_OK, capi.SR_CAND_FALLBACK, capi.SR_CAND_EMPTY, capi.SR_CAND_SKIPPED
 
@@ -116,9 +119,16 @@ class SeqInput:
         return self._ref[key]
 
 
-def from_scenario(nodes, spot_pods, cands) -> SeqInput:
+def from_scenario(nodes, spot_pods, cands, volumes=None, stamped: Optional[str] = None) -> SeqInput:
+    """`stamped`: the input's name; its pods then carry pod stamps (sr_cluster.pod_stamp), without which the
+    encoder never reuses the candidate side between rounds.  A stamp names one pod object for the process's
+    lifetime and every input has a string dictionary of its own, hence stamps no other input shares."""
     flat = [p for c in cands for p in c]
-    sc = Scenario(nodes, spot_pods, flat)
+    stamps = None
+    if stamped is not None:
+        n = sum(len(ps) for ps in spot_pods) + len(flat)
+        stamps = [(1 << 63) | (zlib.crc32(stamped.encode()) << 24) | (i + 1) for i in range(n)]
+    sc = Scenario(nodes, spot_pods, flat, volumes=volumes, stamps=stamps)
     cand_off = np.cumsum([0] + [len(c) for c in cands]).astype(np.int32)
     cand_pods = np.arange(sc.q0, sc.q0 + len(flat), dtype=np.int32)
     return SeqInput(sc.ptr, sc.spot, sc.node_pod_off, sc.node_pod_idx, cand_off, cand_pods, keep=sc)
@@ -149,6 +159,77 @@ BUILDERS["c3-tight"] = lambda: from_synth(SynthCluster(3, seed=41, n_on_demand=3
 FALLBACK_STOPS = {0: 5, 13: 6, 25: 6, 31: 10}  # seed -> the candidate the pass stops at, after two drains
 for _s in FALLBACK_STOPS:
     BUILDERS["fallback-%d" % _s] = lambda s=_s: from_scenario(*rand_scenario(s, fallback=True, **SMALL))
+
+# Volume, spread and extension-record state that moves between rounds.  The facts test_sequence_reference.py
+# asserts: name -> (drains, stop, stop candidate, divergence()).  A FALLBACK stop is "static" when the candidate is
+# FALLBACK from the base snapshot too, "dynamic" (DYNAMIC_STOPS) when only the snapshot the earlier drains leave
+# makes it one.
+END, FALLBACK = capi.SR_SEQ_END, capi.SR_SEQ_FALLBACK
+RECORDED = {
+    "vol-5": (5, END, -1, (2, 3, 2, 8)),
+    "vol-11": (7, END, -1, (0, 5, 0, 7)),
+    "vol-22": (4, END, -1, (4, 3, 2, 9)),
+    "vol-26": (7, END, -1, (1, 5, 0, 6)),
+    "vol-17": (6, FALLBACK, 7, (1, 3, 0, 4)),
+    "vol-10": (3, FALLBACK, 8, (1, 2, 0, 5)),
+    "spread-8": (6, END, -1, (6, 5, 0, 11)),
+    "spread-10": (6, END, -1, (4, 5, 1, 10)),
+    "spread-22": (9, END, -1, (1, 6, 0, 7)),
+    "spread-0": (5, FALLBACK, 10, (1, 1, 0, 3)),
+    "spread-2": (5, FALLBACK, 5, (0, 3, 0, 3)),
+    "replicas-0": (3, END, -1, (0, 2, 0, 2)),
+    "initgpu-1": (3, END, -1, (1, 1, 0, 2)),
+    "realistic-40": (22, END, -1, (0, 16, 0, 231)),
+    "realistic-80": (24, END, -1, (0, 18, 1, 231)),
+    "realistic-120": (28, END, -1, (1, 25, 6, 230)),
+}
+for _n in RECORDED:
+    _kind, _s = _n.split("-")
+    _s = int(_s)
+    if _kind == "vol":
+        BUILDERS[_n] = lambda s=_s, n=_n: from_scenario(*rand_volume_scenario(s), stamped=n)
+    elif _kind == "spread":
+        BUILDERS[_n] = lambda s=_s, n=_n: from_scenario(*rand_spread_scenario(s), stamped=n)
+    elif _kind == "replicas":
+        BUILDERS[_n] = lambda s=_s, n=_n: from_scenario(*rand_spread_replicas(s), stamped=n)
+    elif _kind == "initgpu":
+        BUILDERS[_n] = lambda s=_s, n=_n: from_scenario(*init_and_gpu_scenario(s), stamped=n)
+    else:
+        BUILDERS[_n] = lambda s=_s: from_synth(SynthCluster(3, seed=41, n_on_demand=300, n_spot=s, **REALISTIC))
+
+
+def volflip(which: str) -> SeqInput:
+    """Candidates 3 and 5 bring the same attachable volume V: from the base snapshot no spot node holds it and
+    all seven candidates are planned; once candidate 3 has drained (round 4, the encoder reusing the candidate
+    side since round 3), a spot node holds V and candidate 5 belongs to the reference path."""
+    nodes = [Node("s%d" % i, cpu_milli=4000) for i in range(4)]
+    world = VolumeWorld()
+    if which == "ebs":
+        world = VolumeWorld(pvcs=[PersistentVolumeClaim("q", volume_name="pv-q")],
+                            pvs=[PersistentVolume("pv-q", kind="aws-ebs", volume_id="vol-1")])
+
+    def vol():
+        if which == "ebs":
+            return Volume(name="q", claim="q")
+        return Volume(name="pd", gce_pd="pd7", read_only=which == "gce_ro")
+
+    def pod(name, *vols, cpu=100):
+        return Pod(name, containers=[Container(cpu_milli=cpu)], volumes=list(vols))
+
+    cands = [[pod("p0")], [pod("p1", cpu=3900)], [pod("p2")], [pod("v3", vol())], [pod("p4")],
+             [pod("v5", vol()), pod("q5")], [pod("p6")]]
+    return from_scenario(nodes, [[] for _ in nodes], cands, volumes=world, stamped="volflip-" + which)
+
+
+VOLFLIP = ["volflip-gce_ro", "volflip-gce_rw", "volflip-ebs"]
+for _n in VOLFLIP:
+    BUILDERS[_n] = lambda w=_n.split("-")[1]: volflip(w)
+    RECORDED[_n] = (5, FALLBACK, 5, None)  # the divergence is not part of these inputs' contract
+DYNAMIC_STOPS = ["spread-2"] + VOLFLIP
+# The round whose prepare is the first to classify the stop candidate FALLBACK (round k + 1 sees k drains).  The
+# encoder saves an input on its first encode, builds the reuse index on the second and reuses from the third:
+# a planner that starts cold can have reused a round before the flip only when this is 4 or more.
+FLIP_ROUND = {"spread-2": 2, "volflip-gce_ro": 5, "volflip-gce_rw": 5, "volflip-ebs": 5}
 
 _inputs: Dict[str, SeqInput] = {}
 

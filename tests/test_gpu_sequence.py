@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from oracle_lib import oracle_plan
-from sequence_ref import BUILDERS, FALLBACK_STOPS, SKIPPED, divergence, from_synth, get_input
+from sequence_ref import (BUILDERS, DYNAMIC_STOPS, FALLBACK_STOPS, FLIP_ROUND, RECORDED, SKIPPED, VOLFLIP, divergence,
+                          from_synth, get_input)
 from spotplanner import capi
 from spotplanner.planner import PlannerError
 from spotplanner.rescheduler import plan_arrays, plan_sequence_arrays
@@ -75,7 +76,7 @@ def test_sequence_matches_reference_pass(checker, name):
     check_sequence(checker, get_input(name))
 
 
-@pytest.mark.parametrize("name", ["plain-4", "features-11", "c5"])
+@pytest.mark.parametrize("name", ["plain-4", "features-11", "c5", "vol-11", "spread-22", "realistic-80"])
 def test_budgets(checker, name):
     inp = get_input(name)
     lib = capi.load_planner()
@@ -121,6 +122,117 @@ def test_fallback_stop_and_resume(checker, seed):
         assert np.all(got2.status[:got.stop_cand + 1] == SKIPPED)
     finally:
         capi.load_planner().sr_snapshot_destroy(h)
+
+
+def record_rounds(record_property, what, got):
+    print("%s: rounds %d, with K0 %d, reused %d" % (what, got.rounds, got.rounds_k0, got.rounds_reused))
+    record_property("rounds", got.rounds)
+    record_property("rounds_k0", got.rounds_k0)
+    record_property("rounds_reused", got.rounds_reused)
+
+
+@pytest.mark.parametrize("start", ["cold", "warm"])
+@pytest.mark.parametrize("name", DYNAMIC_STOPS)
+def test_dynamic_fallback_stop_and_resume(name, start, record_property):
+    """A candidate the base snapshot plans turns into a reference-path candidate against the snapshot the earlier
+    drains leave (volflip-*: a spot node now holds its attachable volume; spread-2: the drained pods are on the
+    spot nodes its spread constraints read), while the encoder is reusing the candidate side: the classification
+    is that round's prepare's, not the first one's.
+
+    "cold" is a new planner: it reuses from its third round, so the flip meets a reusing planner on the
+    volflip-* inputs (round 5).  On spread-2 the first drain already turns candidate 5 (FLIP_ROUND: round 2, a
+    fallback decided by the snapshot's counts, with which the encoder builds no reuse index), so a cold planner
+    runs its 6 rounds with rounds_reused == 0 whatever it does; "warm" plans the same input three times from the
+    base snapshot first, so that the sequence's first round is already a reusing one and the flip has to be
+    noticed by the reuse itself on every input."""
+    inp = get_input(name)
+    ref, states = inp.reference()
+    stop_cand = RECORDED[name][2]
+    ck = make_checker()
+    h = inp.product_snapshot()
+    try:
+        if start == "warm":
+            hb = inp.product_snapshot()
+            try:
+                for _ in range(3):
+                    plan_arrays(ck, hb, inp.ptr, inp.cand_off, inp.cand_pods)
+            finally:
+                capi.load_planner().sr_snapshot_destroy(hb)
+            assert ck.timing().enc_reused == 1
+        got = run_sequence(ck, inp, h)
+        record_rounds(record_property, "%s %s" % (name, start), got)
+        assert (got.stop, got.stop_cand) == (capi.SR_SEQ_FALLBACK, stop_cand)
+        assert_equals_reference(inp, h, got, ref, states)
+        if start == "warm" or FLIP_ROUND[name] >= 4:
+            assert got.rounds_reused >= 1  # the flip met a planner that had been reusing
+        ref2, states2 = inp.reference(None, stop_cand + 1, after=(None, 0))
+        got2 = run_sequence(ck, inp, h, None, stop_cand + 1)
+        assert_equals_reference(inp, h, got2, ref2, states2)
+        assert np.all(got2.status[:stop_cand + 1] == SKIPPED)
+        if name in VOLFLIP:
+            assert list(ref2.drained) == [6] and list(got2.drained) == [6]
+    finally:
+        capi.load_planner().sr_snapshot_destroy(h)
+        ck.close()
+
+
+REALISTIC_FORMS = {
+    "default": {},
+    "k0_every_round": dict(SR_K0_SKIP=0),
+    "k0_whole": dict(SR_K0_INCREMENTAL=0),
+    "pod_order": dict(SR_K2_MODE=1),
+    "general_kernel": dict(SR_K2_NODE_KERNEL=0),
+    "whole_node_section": dict(SR_NODE_PATCH=0),
+    "wide_rows": dict(SR_K2_NARROW=0),
+    "one_plan_slot": dict(SR_PLAN_SLOTS=1),
+}
+REALISTIC_BUDGET = 10
+
+
+@pytest.mark.parametrize("form", sorted(REALISTIC_FORMS))
+def test_realistic_forms(form, record_property):
+    """The floor under the extension-record instances (k2_node<G, XT>, the x windows) and the other K2 and K0
+    forms, on the input most of whose candidates carry extension records (init-container accounting, shared
+    scalar names and volume-limit keys; test_realistic_80_has_extension_record_candidates)."""
+    ck = make_checker(**REALISTIC_FORMS[form])
+    try:
+        got = check_sequence(ck, get_input("realistic-80"), REALISTIC_BUDGET)
+    finally:
+        ck.close()
+    record_rounds(record_property, "realistic-80 %s" % form, got)
+    assert got.rounds == REALISTIC_BUDGET
+    if form == "k0_every_round":
+        assert got.rounds_k0 == got.rounds
+
+
+def test_drained_only_call_then_other_workloads(checker):
+    """status == NULL and node_of_pod == NULL: the call returns while the last round's K2 and ledger kernel may
+    still run.  The next call on the context, a larger plan on another cluster (buffers move), and a sequence
+    after it are the oracle's."""
+    inp, c5, vol = get_input("realistic-80"), get_input("c5"), get_input("vol-11")
+    ref, states = inp.reference(5)
+    o5 = oracle_plan(c5.oracle_snapshot(), c5.ptr, c5.cand_off, c5.cand_pods, mode=1, threads=8)
+    lib = capi.load_planner()
+    h, h5 = inp.product_snapshot(), c5.product_snapshot()
+    try:
+        n = len(inp.cand_off) - 1
+        c = capi.sr_candidates(n, capi.ptr(inp.cand_off, capi.P32), capi.ptr(inp.cand_pods, capi.P32), None)
+        drained = np.full(5, -1, np.int32)
+        o = capi.sr_sequence_out()
+        o.max_drains = 5
+        o.drained = capi.ptr(drained, capi.P32)
+        st = lib.sr_plan_sequence(checker.handle, h, inp.ptr, ctypes.byref(c), ctypes.byref(o))
+        p = plan_arrays(checker, h5, c5.ptr, c5.cand_off, c5.cand_pods)  # no other call in between
+        assert st == capi.SR_OK, checker.last_error()
+        assert list(drained[:o.n_drained]) == list(ref.drained)
+        assert (o.stop, o.stop_cand) == (ref.stop, ref.stop_cand) == (capi.SR_SEQ_BUDGET, -1)
+        assert node_states(h, len(inp.spot)) == states
+        compare_plans(o5, p, c5.cand_off)
+        assert np.array_equal(p.status, o5["status"]) and np.array_equal(p.node_of_pod, o5["node_of_pod"])
+    finally:
+        lib.sr_snapshot_destroy(h)
+        lib.sr_snapshot_destroy(h5)
+    check_sequence(checker, vol)
 
 
 K0_FORMS = {"default": {}, "k0_every_round": dict(SR_K0_SKIP=0), "k0_whole": dict(SR_K0_INCREMENTAL=0)}

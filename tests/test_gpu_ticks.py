@@ -532,3 +532,98 @@ def test_ticks_affinity_variant_reuse(checker, config):
         finally:
             lib.sr_snapshot_destroy(h)
     assert reused >= 6, reused
+
+
+def _spot_state_ticks(sc, nm, cand_pods, rng):
+    """Twelve ticks' extra (pod, spot position) pairs for the realistic variant: candidate pods that list a scalar
+    (and bring no attachable volume) and candidate pods with an attachable volume, placed on spot nodes as well.
+    Ticks 1-3 add three scalar pods each, 4 clears; 5 fills every spot node that allocates the GPU name beyond
+    its allocatable, 6 clears; 7-9 add three volume pods each, 10 clears; 11 adds three of either."""
+    cl, n = sc.cluster, sc.n_pods
+    has_scalar = np.diff(np.ctypeslib.as_array(cl.pod_scalar_off, shape=(n + 1,)))[cand_pods] > 0
+    has_volume = np.diff(np.ctypeslib.as_array(cl.volumes.contents.att_off, shape=(n + 1,)))[cand_pods] > 0
+    G, V = cand_pods[has_scalar & ~has_volume], cand_pods[has_volume]
+    node_off = np.ctypeslib.as_array(cl.node_scalar_off, shape=(sc.n_nodes + 1,))
+    alloc = np.ctypeslib.as_array(cl.node_scalar_alloc, shape=(max(1, int(node_off[-1])),))
+    acc = np.ctypeslib.as_array(cl.pod_scalar_acc, shape=(max(1, int(cl.pod_scalar_off[n])),))
+    assert np.all(np.diff(node_off) <= 1) and np.all(acc == 1)  # one scalar name (the GPU), one unit per pod
+    assert len(G) >= 100 and len(V) >= 100
+
+    def pick(pool, k):
+        return [(int(rng.choice(pool)), int(rng.integers(len(nm.spot)))) for _ in range(k)]
+
+    ticks, extra = [], []
+    for tick in range(12):
+        if tick in (4, 6, 10):
+            extra = []
+        elif 1 <= tick <= 3:
+            extra = extra + pick(G, 3)
+        elif tick == 5:
+            k = 0
+            for pos, node in enumerate(nm.spot):
+                if node_off[node + 1] > node_off[node]:
+                    for _ in range(int(alloc[node_off[node]]) + 1):
+                        extra.append((int(G[k % len(G)]), pos))
+                        k += 1
+        elif 7 <= tick <= 9:
+            extra = extra + pick(V, 3)
+        elif tick == 11:
+            extra = pick(V, 3) + pick(G, 3)
+        ticks.append(list(extra))
+    return ticks, has_scalar
+
+
+@pytest.mark.parametrize("config", [3, 5])
+def test_ticks_realistic_variant_spot_volumes_and_scalars(config, record_property):
+    """The realistic variant with spot nodes that gain and lose extended-resource usage and attachable volumes
+    between ticks: the scalar rows (empty rows turning non-empty, GPU nodes filling up and emptying) and the
+    volume-limit rows move under a reused candidate side, and a candidate pod's volume appearing on a spot node
+    ends the reuse and sends its candidate to the reference path.  One planner of its own, the same candidates
+    every tick, a fresh snapshot per tick; every plan equals the oracle's."""
+    from spotplanner.planner import PredicateChecker
+    from spotplanner.synth import REALISTIC
+    sc = SynthCluster(config, seed=24, n_on_demand=150, n_spot=400, **REALISTIC)
+    lib = capi.load_planner()
+    nm = new_node_map(lib.sr_new_node_map, sc.ptr, sc.n_nodes, sc.n_pods, sc.od_label, sc.spot_label)
+    cand_off, cand_pods = build_candidates(nm, sc.pod_flags())
+    ticks, wants_gpu = _spot_state_ticks(sc, nm, cand_pods, np.random.default_rng(config))
+    lists = [_with_extra(nm, sc.n_nodes, extra) for extra in ticks]
+    # the preconditions, from the oracle alone
+    want = [oracle_plan(OracleSnapshot(sc.ptr, nm.spot, off, idx), sc.ptr, cand_off, cand_pods, mode=1, threads=8)
+            for off, idx in lists]
+    fallbacks = [int(np.sum(o["status"] == capi.SR_CAND_FALLBACK)) for o in want]
+    print("oracle FALLBACK candidates per tick:", fallbacks)
+    assert all(fallbacks[t] == 0 for t in (0, 1, 2, 3, 4, 5, 6, 10)), fallbacks
+    assert all(fallbacks[t] >= 1 for t in (7, 8, 9, 11)), fallbacks
+    assert not np.any(want[5]["node_of_pod"][wants_gpu] >= 0)
+    assert np.any(want[6]["node_of_pod"][wants_gpu] >= 0)
+    moved = [not np.array_equal(want[t]["node_of_pod"], want[t + 1]["node_of_pod"]) for t in range(11)]
+    assert sum(moved) >= 6, moved
+
+    ck = PredicateChecker(0)
+    reused = []
+    try:
+        for tick, (off, idx) in enumerate(lists):
+            h = ctypes.c_void_p()
+            assert lib.sr_snapshot_create(sc.ptr, capi.ptr(nm.spot, capi.P32), len(nm.spot),
+                                          capi.ptr(off, capi.P32), capi.ptr(idx, capi.P32),
+                                          ctypes.byref(h)) == capi.SR_OK
+            try:
+                p = plan_arrays(ck, h, sc.ptr, cand_off, cand_pods)
+            finally:
+                lib.sr_snapshot_destroy(h)
+            t = ck.timing()
+            print("tick %d: enc_reused %d, k0_columns %d, enc_pod_patches %d" % (tick, t.enc_reused, t.k0_columns,
+                                                                                 t.enc_pod_patches))
+            record_property("tick%d" % tick, "enc_reused=%d k0_columns=%d enc_pod_patches=%d"
+                            % (t.enc_reused, t.k0_columns, t.enc_pod_patches))
+            reused.append(int(t.enc_reused))
+            o = want[tick]
+            assert np.array_equal(p.status, o["status"]), tick
+            assert np.array_equal(p.node_of_pod, o["node_of_pod"]), tick
+            assert p.winner == o["winner"], tick
+            assert p.first_fallback == o["first_fallback"], tick
+    finally:
+        ck.close()
+    assert reused[2:7] == [1] * 5, reused  # scalar changes alone do not end the reuse
+    assert 0 in [reused[t] for t in (7, 8, 9, 11)], reused  # a held volume does

@@ -24,10 +24,10 @@ import pytest
 from helpers import Scenario
 from oracle_lib import load_oracle, oracle_plan
 from randcluster import rand_scenario
+from scenario_gen import G, init_and_gpu_scenario
 from spotplanner import capi
 from spotplanner.model import Container, GiB, Node, Pod
 
-G = "nvidia.com/gpu"
 OK, FB = capi.SR_CAND_OK, capi.SR_CAND_FALLBACK
 
 
@@ -192,33 +192,6 @@ def test_gpu_random_scalar_clusters(checker, seed):
                 p.containers[0].cpu_milli = 10
     _, o, p = run_scenario(checker, nodes, spot_pods, cands)
     assert sum(int(s) != FB for s in p.status) >= 1
-
-
-def init_and_gpu_scenario(seed):
-    """Random clusters where most pods carry init containers (fit request !=
-    AddPod accounting) and most candidates list one GPU name in several pods
-    (a running scalar state per touched node), some hugepages too."""
-    import random
-    nodes, spot_pods, cands = rand_scenario(9100 + seed, n_spot=6 + seed % 20, n_cand=12, max_pods=4 + seed % 12,
-                                            features=seed % 2 == 0)
-    r = random.Random(seed)
-    for n in nodes:
-        if r.random() < 0.8:
-            n.scalar = {G: r.choice([0, 1, 2, 4, 8]), "hugepages-2Mi": r.choice([0, 8 << 20])}
-    for c in cands:
-        gpu_cand = r.random() < 0.7
-        for p in c:
-            if r.random() < 0.5:
-                p.init_containers = [Container(cpu_milli=r.choice([200, 1500, 3000]),
-                                               memory=r.choice([0, 1 * GiB, 6 * GiB]),
-                                               scalar={G: r.choice([1, 2])} if gpu_cand and r.random() < 0.3 else {})]
-            if gpu_cand and r.random() < 0.6:
-                p.containers[0].scalar = {G: r.choice([0, 1, 1, 2])}
-                if r.random() < 0.2:
-                    p.containers[0].scalar["hugepages-2Mi"] = r.choice([2 << 20, 4 << 20])
-                if p.containers[0].cpu_milli == 0:
-                    p.containers[0].cpu_milli = 10
-    return nodes, spot_pods, cands
 
 
 def test_oracle_plans_init_and_shared_scalar_candidates():

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from oracle_lib import oracle_plan
-from sequence_ref import BUILDERS, FALLBACK_STOPS, OK, SKIPPED, divergence, from_synth, get_input, reference_sequence
+from sequence_ref import (BUILDERS, DYNAMIC_STOPS, EMPTY, FALLBACK_STOPS, FB, FLIP_ROUND, OK, RECORDED, SKIPPED,
+                          VOLFLIP, divergence, from_synth, get_input, reference_sequence)
 from spotplanner import capi
 from spotplanner.synth import SynthCluster
 
@@ -42,7 +43,11 @@ def test_budget_one_is_the_reference_tick(name):
     assert np.all(ref.status[w + 1:] == SKIPPED)
 
 
-@pytest.mark.parametrize("name", sorted(n for n in BUILDERS if not n.startswith("fallback")))
+def _stops_at_fallback(name):
+    return name.startswith("fallback") or (name in RECORDED and RECORDED[name][1] == capi.SR_SEQ_FALLBACK)
+
+
+@pytest.mark.parametrize("name", sorted(n for n in BUILDERS if not _stops_at_fallback(n)))
 def test_commits_matter(name):
     """Some judged candidate's status or mapping differs from its plan on the base snapshot."""
     inp = get_input(name)
@@ -64,6 +69,83 @@ def test_synthetic_inputs_diverge_as_recorded():
     assert (len(ref.drained), divergence(get_input("c3-affinity"), ref)[1]) == (42, 38)
     ref, _ = get_input("c3-tight").reference()
     assert (len(ref.drained), divergence(get_input("c3-tight"), ref)[2]) == (38, 20)
+
+
+@pytest.mark.parametrize("name", sorted(RECORDED))
+def test_volume_spread_and_extension_inputs_as_recorded(name):
+    """The drains, the stop and the divergence from the base plan of the inputs with volumes, spread constraints
+    and extension records, exactly; a dynamic stop's candidate is planned from the base snapshot."""
+    inp = get_input(name)
+    ref, _ = inp.reference()
+    drains, stop, stop_cand, div = RECORDED[name]
+    assert (len(ref.drained), ref.stop, ref.stop_cand) == (drains, stop, stop_cand)
+    if div is not None:
+        assert tuple(int(x) for x in divergence(inp, ref)) == div
+    base = inp.base_plan()["status"]
+    if name in DYNAMIC_STOPS:
+        assert base[stop_cand] != FB and not np.any(base == FB)
+        assert ref.status[stop_cand] == FB and np.all(ref.status[stop_cand + 1:] == SKIPPED)
+        flips = []  # is the stop candidate FALLBACK from the snapshot k drains leave?
+        for k in range(drains + 1):
+            osnap = inp.oracle_snapshot()
+            if k:
+                reference_sequence(osnap, inp.ptr, inp.cand_off, inp.cand_pods, k)
+            flips.append(oracle_plan(osnap, inp.ptr, inp.cand_off, inp.cand_pods, mode=1)["status"][stop_cand] == FB)
+            osnap.close()
+        assert flips.index(True) + 1 == FLIP_ROUND[name] and all(flips[FLIP_ROUND[name] - 1:])
+    elif stop == capi.SR_SEQ_FALLBACK:
+        assert base[stop_cand] == FB  # static
+    if name in VOLFLIP:
+        assert np.all(base == OK)
+        assert list(ref.drained) == [0, 1, 2, 3, 4]
+        assert list(ref.status) == [OK, OK, OK, OK, OK, FB, SKIPPED] == [-1, -1, -1, -1, -1, -2, -4]
+
+
+def _arr(p, n):
+    return np.ctypeslib.as_array(p, shape=(n,))
+
+
+def extension_record_candidates(inp, judged):
+    """The judged candidates with a reason for extension records, read off the cluster arrays: (candidates with a
+    pod whose AddPod accounting differs from its fit request and which is not the candidate's last pod,
+    candidates where two pods list one scalar name or one volume-limit key, candidates with either)."""
+    cl = inp.keep[0].cluster
+    n = cl.pods.n
+    differs = np.zeros(n, bool)
+    for req, acc in ((cl.pods.req_milli_cpu, cl.acc_milli_cpu), (cl.pods.req_memory, cl.acc_memory),
+                     (cl.pods.req_ephemeral, cl.acc_ephemeral)):
+        differs |= _arr(req, n) != _arr(acc, n)
+    s_off = _arr(cl.pod_scalar_off, n + 1)
+    s_name = _arr(cl.pod_scalar_name, max(1, int(s_off[-1])))
+    v = cl.volumes.contents
+    a_off = _arr(v.att_off, n + 1)
+    a_key = _arr(v.att_key, max(1, int(a_off[-1])))
+    init = shared = either = 0
+    for c in judged:
+        pods = inp.cand_pods[inp.cand_off[c]:inp.cand_off[c + 1]]
+        by_init = bool(np.any(differs[pods[:-1]]))
+        seen, by_shared = set(), False
+        for p in pods:
+            names = {("scalar", int(x)) for x in s_name[s_off[p]:s_off[p + 1]]}
+            names |= {("limit", int(x)) for x in a_key[a_off[p]:a_off[p + 1]]}
+            by_shared |= bool(names & seen)
+            seen |= names
+        init += by_init
+        shared += by_shared
+        either += by_init or by_shared
+    return init, shared, either
+
+
+def test_realistic_80_has_extension_record_candidates():
+    """The forms of test_gpu_sequence.py run realistic-80 for its extension records: at least 20 of its judged
+    candidates have a reason for them (a guard for the witness, not a measurement)."""
+    inp = get_input("realistic-80")
+    ref, _ = inp.reference()
+    judged = [c for c in range(len(ref.status)) if ref.status[c] not in (SKIPPED, FB, EMPTY)]
+    init, shared, either = extension_record_candidates(inp, judged)
+    print("realistic-80: %d judged, init accounting %d, shared names %d, either %d" % (len(judged), init, shared,
+                                                                                      either))
+    assert either >= 20
 
 
 def test_full_size_like_c3_is_no_sequence_input():

@@ -17,22 +17,17 @@ snapshot; a candidate with a pod whose constraint counts an earlier pod of the
 candidate goes to the reference path, as does a selector that fails to build.
 Checked on the oracle (CPU) and the GPU (C-ABI), plus random clusters on the
 GPU against the oracle."""
-import random
-
 import numpy as np
 import pytest
 
 from helpers import Scenario
 from oracle_lib import oracle_plan
-from randcluster import rand_scenario
+from scenario_gen import WEB, H, Z, rand_spread_replicas, rand_spread_scenario, spread, zc
 from spotplanner import capi
 from spotplanner.model import (Container, LabelSelector, LabelSelectorRequirement, Node, NodeSelectorRequirement,
-                               NodeSelectorTerm, Pod, TopologySpreadConstraint)
+                               NodeSelectorTerm, Pod)
 
 OK, FB = capi.SR_CAND_OK, capi.SR_CAND_FALLBACK
-Z = "topology.kubernetes.io/zone"
-H = "kubernetes.io/hostname"
-WEB = LabelSelector(match_labels={"app": "web"})
 
 
 def zone_nodes():
@@ -48,15 +43,6 @@ def web(name, ns="default", cpu=100, **kw):
 
 def other(name, ns="default", cpu=100, labels=None):
     return Pod(name, namespace=ns, containers=[Container(cpu_milli=cpu)], labels=labels or {"app": "other"})
-
-
-def spread(pod, *cs):
-    pod.topology_spread = list(cs)
-    return pod
-
-
-def zc(skew=1, sel=WEB, key=Z, when="DoNotSchedule"):
-    return TopologySpreadConstraint(skew, key, when, sel)
 
 
 def cases():
@@ -192,77 +178,6 @@ def test_spread_without_tables_flags_pod():
     assert not enc.a["flags"][0] & capi.SR_POD_FB_TOPOLOGY_SPREAD
     q = spread(web("q"), zc(when="ScheduleAnyway"))
     assert not encode_cluster(zone_nodes(), [q], spread_tables=False).a["flags"][0] & capi.SR_POD_FB_TOPOLOGY_SPREAD
-
-
-def rand_spread_scenario(seed):
-    """Random zone / rack clusters with web / api pods in two namespaces,
-    some terminating, and spread constraints on a share of the candidate
-    pods (several per pod, shared keys, selectors of every operator, nil)."""
-    r = random.Random(5150 + seed)
-    nodes, spot_pods, cands = rand_scenario(6600 + seed, n_spot=6 + seed % 25, n_cand=12, max_pods=5,
-                                            features=False)
-    zones = ["z%d" % i for i in range(1 + seed % 4)]
-    for i, n in enumerate(nodes):
-        n.labels = dict(n.labels)
-        n.labels[H] = n.name
-        if r.random() < 0.85:
-            n.labels[Z] = r.choice(zones + [""] if seed % 5 == 0 else zones)
-        if r.random() < 0.5:
-            n.labels["example.com/rack"] = "r%d" % r.randrange(3)
-    apps = ["web", "api", "db"]
-    for ps in spot_pods:
-        for p in ps:
-            p.namespace = r.choice(["default", "default", "other"])
-            p.labels = {"app": r.choice(apps)} if r.random() < 0.9 else {}
-            if r.random() < 0.1:
-                p.deletion_age_s = 3.0
-
-    def rand_sel():
-        x = r.random()
-        if x < 0.1:
-            return None
-        if x < 0.6:
-            return LabelSelector(match_labels={"app": r.choice(apps)})
-        op = r.choice(["In", "NotIn", "Exists", "DoesNotExist"])
-        vals = r.sample(apps, r.randint(1, 2)) if op in ("In", "NotIn") else []
-        return LabelSelector(match_expressions=[LabelSelectorRequirement("app", op, vals)])
-
-    for c in cands:
-        for p in c:
-            p.namespace = "default" if r.random() < 0.8 else "other"
-            p.labels = {"app": r.choice(apps)}
-            if r.random() < 0.5:
-                p.topology_spread = [zc(skew=r.choice([1, 1, 2]), sel=rand_sel(),
-                                        key=r.choice([Z, Z, H, "example.com/rack"]))
-                                     for _ in range(r.choice([1, 1, 2]))]
-                if r.random() < 0.2:
-                    p.node_selector = {Z: r.choice(zones)}
-    return nodes, spot_pods, cands
-
-
-def rand_spread_replicas(seed):
-    """Large candidates of Deployment replicas spread over zones (65-230 pods
-    per candidate: 2-4 pod groups of the domain path), with a hostname
-    constraint on some, over pools whose nodes already run replicas."""
-    r = random.Random(8080 + seed)
-    zones = ["z%d" % i for i in range(2 + seed % 4)]
-    n_spot = 30 + seed % 40
-    nodes = [Node("s%d" % i, cpu_milli=64000, memory=256 * 2 ** 30, pods=110,
-                  labels={Z: r.choice(zones), H: "s%d" % i}) for i in range(n_spot)]
-    apps = ["web", "api"]
-    spot_pods = [[Pod("b%d_%d" % (i, j), namespace="default", containers=[Container(cpu_milli=r.choice([100, 250]))],
-                      labels={"app": r.choice(apps)}) for j in range(r.randrange(4))] for i in range(n_spot)]
-    cands = []
-    for ci in range(3):
-        n = 65 + r.randrange(166)
-        app = r.choice(apps)
-        cs = [zc(skew=r.choice([1, 2, 3]), sel=LabelSelector(match_labels={"app": app}))]
-        if r.random() < 0.3:
-            cs.append(zc(skew=r.choice([2, 4]), sel=LabelSelector(match_labels={"app": app}), key=H))
-        cands.append([spread(Pod("c%d_%d" % (ci, j), namespace="default",
-                                 containers=[Container(cpu_milli=r.choice([50, 100, 250, 500]))],
-                                 labels={"app": app}), *cs) for j in range(n)])
-    return nodes, spot_pods, cands
 
 
 @pytest.mark.parametrize("seed", range(6))

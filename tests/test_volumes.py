@@ -25,22 +25,17 @@ The reference path takes: claims with WaitForFirstConsumer binding still
 unbound, RBD volumes, a pod whose attachable volume a spot node already holds,
 two pods of one candidate sharing one, more than two shared limit keys / scalar
 names per candidate.  Checked on the oracle (CPU) and the GPU (C-ABI)."""
-import random
-
 import numpy as np
 import pytest
 
 from helpers import Scenario
 from oracle_lib import oracle_plan
-from randcluster import rand_scenario
+from scenario_gen import EBS_CSI, TR, TZ, rand_volume_scenario, req, term
 from spotplanner import capi
-from spotplanner.model import (Container, Node, NodeSelectorRequirement, NodeSelectorTerm, PersistentVolume,
-                               PersistentVolumeClaim, Pod, Volume, VolumeWorld)
+from spotplanner.model import Container, Node, PersistentVolume, PersistentVolumeClaim, Pod, Volume, VolumeWorld
 
 OK, FB = capi.SR_CAND_OK, capi.SR_CAND_FALLBACK
-TZ, TR = "topology.kubernetes.io/zone", "topology.kubernetes.io/region"
 BZ = "failure-domain.beta.kubernetes.io/zone"
-EBS_CSI = "ebs.csi.aws.com"
 
 
 
@@ -89,14 +84,6 @@ def pv(name, zone=None, labels=None, terms=None, kind="csi", vid=None):
     if zone is not None:
         lab[TZ] = zone
     return PersistentVolume(name, kind=kind, volume_id=vid or name, labels=lab, node_affinity=terms)
-
-
-def term(*reqs, fields=()):
-    return NodeSelectorTerm(list(reqs), list(fields))
-
-
-def req(k, op, *vals):
-    return NodeSelectorRequirement(k, op, list(vals))
 
 
 def cases():
@@ -261,57 +248,6 @@ def test_volume_tables_absent_flag_pods():
     assert enc.a["flags"][0] & capi.SR_POD_FB_VOLUMES
     enc = encode_cluster(nodes4(), [p], volumes=world(("q", pv("v1"))))
     assert not enc.a["flags"][0] & capi.SR_POD_FB_VOLUMES
-
-
-def rand_volume_scenario(seed):
-    """Random clusters whose pods carry claims (CSI / EBS / GCE PD PVs with zone
-    labels and node affinity), inline ISCSI / GCE PD / EBS disks, under CSINode
-    and Allocatable limits; some claims unbound or waiting for a consumer."""
-    r = random.Random(seed)
-    nodes, spot_pods, cands = rand_scenario(9500 + seed, n_spot=6 + seed % 14, n_cand=10, max_pods=3 + seed % 6,
-                                            features=seed % 3 == 0)
-    zones = ["z1", "z2", "z3"]
-    for i, n in enumerate(nodes):
-        if r.random() < 0.8:
-            n.labels[TZ] = r.choice(zones)
-        if r.random() < 0.5:
-            n.labels[TR] = "r1"
-        if r.random() < 0.3:
-            n.scalar["attachable-volumes-aws-ebs"] = r.choice([0, 1, 2, 3])
-    pvcs, pvs, vid = [], [], [0]
-
-    def new_claim(ns):
-        vid[0] += 1
-        name = "c%d" % vid[0]
-        x = r.random()
-        if x < 0.05:
-            pvcs.append(PersistentVolumeClaim(name, namespace=ns))
-        elif x < 0.1:
-            pvcs.append(PersistentVolumeClaim(name, namespace=ns, binding_mode="WaitForFirstConsumer"))
-        else:
-            kind = r.choice(["csi", "csi", "aws-ebs", "gce-pd", "nfs"])
-            labels = {TZ: r.choice(zones + ["z1__z2"])} if r.random() < 0.5 else {}
-            terms = None
-            if r.random() < 0.3:
-                terms = [term(req(TZ, "In", *r.sample(zones, r.choice([1, 2]))))]
-                if r.random() < 0.3:
-                    terms.append(term(req(TR, "Exists")))
-            pvs.append(PersistentVolume("pv" + name, kind=kind, volume_id="v%d" % vid[0], labels=labels,
-                                        node_affinity=terms))
-            pvcs.append(PersistentVolumeClaim(name, namespace=ns, volume_name="pv" + name))
-        return Volume(name=name, claim=name)
-
-    iqns = ["iq1", "iq2", "iq3"]
-    for ps in spot_pods + cands:
-        for p in ps:
-            if r.random() < 0.35:
-                p.volumes.append(new_claim(p.namespace))
-            if r.random() < 0.15:
-                p.volumes.append(Volume(name="isc", iscsi_iqn=r.choice(iqns), read_only=r.random() < 0.5))
-            if r.random() < 0.05:
-                p.volumes.append(Volume(name="pd", gce_pd="pd%d" % r.randrange(1000), read_only=r.random() < 0.5))
-    csi = {n.name: {EBS_CSI: r.choice([1, 2, 4])} for n in nodes if r.random() < 0.6}
-    return nodes, spot_pods, cands, VolumeWorld(pvcs=pvcs, pvs=pvs, csi_limits=csi)
 
 
 def run_volume_scenario(checker, seed):
