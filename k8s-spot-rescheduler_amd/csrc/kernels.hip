@@ -2782,15 +2782,6 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
   k2_finish<PROF>(w, x, status, 2, nbytes, st);
 }
 
-// K2 waves per block: SR_K2_WPB (1, 2, 4), else one wave per block for lists of
-// at most 2,048 entries (the waves spread over every CU, so a long chain wave
-// shares its CU with fewer others: C5 K2 38.2 -> 36.1 us, realistic C3 31.5 ->
-// 30.5, C3 15.0 -> 14.4) and four above (C4: 15,000 waves)
-static inline int k2_waves_per_block(const DevWorkload& w) {
-  if (w.k2_wpb == 1 || w.k2_wpb == 2 || w.k2_wpb == 4) return w.k2_wpb;
-  return w.n_list <= 2048 ? 1 : 4;
-}
-
 // Launch with optional HIP events recorded by the dispatch itself
 // (hipExtLaunchKernelGGL: no event packets or host calls around the kernel).
 template <typename K, typename... A>
@@ -2823,7 +2814,7 @@ hipError_t launch_k2_place_ch(const DevWorkload& w, hipStream_t s, hipEvent_t ev
 template <bool PROF>
 hipError_t launch_k2_node_g(const DevWorkload& w, int G, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   const int n = w.n_list;
-  const int wpb = k2_waves_per_block(w);  // waves per block
+  const int wpb = k2_waves_per_block(w.k2_wpb, n);  // waves per block
   // cooperative blocks first (one candidate each), then wpb candidates per block
   if (w.n_coop < 0 || w.n_coop > n || (w.n_coop > 0 && (wpb != kCoopWaves || w.ext_cand))) return hipErrorInvalidValue;
   const dim3 grid(w.n_coop + (n - w.n_coop + wpb - 1) / wpb), block(64 * wpb);
@@ -2845,7 +2836,7 @@ template hipError_t launch_k2_node_g<true>(const DevWorkload&, int, hipStream_t,
 template <bool PROF>
 hipError_t launch_k2_node_xt_g(const DevWorkload& w, int G, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   const int n = w.n_list;
-  const int wpb = k2_waves_per_block(w);
+  const int wpb = k2_waves_per_block(w.k2_wpb, n);
   const dim3 grid((n + wpb - 1) / wpb), block(64 * wpb);
   const size_t lds = wpb * static_cast<size_t>(64 * G * kNHS + (w.s_head_only ? 64 * G * 4 : 0)) * 8;
   const bool wide = n <= 2048;  // as launch_k2_node_g
@@ -2863,7 +2854,7 @@ template hipError_t launch_k2_node_xt_g<true>(const DevWorkload&, int, hipStream
 template <int CH, bool PROF>
 hipError_t launch_k2_place_ch(const DevWorkload& w, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   const int n = w.n_list;
-  const int wpb = k2_waves_per_block(w);  // waves per block
+  const int wpb = k2_waves_per_block(w.k2_wpb, n);  // waves per block
   const dim3 grid((n + wpb - 1) / wpb), block(64 * wpb);
   launch(k2_place<CH, PROF>, grid, block, wpb * sizeof(K2Lds), s, ev0, ev1, w, w.list, n);
   return hipGetLastError();
@@ -2896,8 +2887,8 @@ template <bool PROF>
 hipError_t launch_k2(const DevWorkload& w, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   const int n = w.n_list;
   if (n <= 0) return hipSuccess;
-  if (!w.dyn_cand && w.k2_mode == 0 && w.max_np >= 1 && w.max_np <= 4 * 64 && w.k2_node_kernel)
-    return launch_k2_node_g<PROF>(w, w.max_np <= 64 ? 1 : (w.max_np <= 128 ? 2 : 4), s, ev0, ev1);
+  if (k2_node_launch(w.dyn_cand != nullptr, w.k2_mode, w.max_np, w.k2_node_kernel))
+    return launch_k2_node_g<PROF>(w, k2_node_groups(w.max_np), s, ev0, ev1);
   const int chunks = (w.Wp + 63) / 64;
   if (chunks <= 1) return launch_k2_place_ch<1, PROF>(w, s, ev0, ev1);
   if (chunks <= 2) return launch_k2_place_ch<2, PROF>(w, s, ev0, ev1);

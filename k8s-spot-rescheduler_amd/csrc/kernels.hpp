@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "launch_shape.hpp"
 #include "progops.hpp"
 
 namespace sr {

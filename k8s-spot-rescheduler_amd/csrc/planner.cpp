@@ -22,6 +22,7 @@
 
 #include "host.hpp"
 #include "kernels.hpp"
+#include "residency.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -77,43 +78,14 @@ struct HostBuf {
 // device-resident records instead of re-encoding and re-uploading them.
 struct Slot {
   sr::Workload wl;
+  sr::Residency res;  // what the buffers below hold (residency.hpp)
   DevBuf arena;
   HostBuf h_arena;
-  uint64_t dev_state_gen = ~0ull;   // encoder state whose node records the device arena holds
-  uint64_t host_state_gen = ~0ull;  // ... and the pinned staging arena
-  uint64_t dev_cand_gen = ~0ull;    // candidate generation (Workload::cand_gen) the device arena holds (its
-                                    //   pod records as of the last K0 run plus none of the pending patches)
-  uint64_t host_cand_gen = ~0ull;   // ... and the staging arena (every patch applied)
-  DevBuf tables;                    // S and T rows (K0 writes, K2 reads)
-  uint64_t tables_cand_gen = ~0ull; // candidate generation, encoder state, thresholds and atoms of the last K0
-  uint64_t tables_state_gen = ~0ull;  //   run on `tables` (incremental K0 / K0-less runs: what changed since)
-  std::vector<int64_t> tables_thr;
-  uint64_t tables_atoms_ver = ~0ull;   // Workload::atoms_ver of the last K0 run
-  std::vector<int32_t> atom_cols;      // inter-pod / spread atom words changed since (reuse encodes)
-  // atom rows changed since version atoms_log_ver (reuse encodes of one
-  // candidate generation): the staging and device copies of an older version
-  // that is atoms_log_ver take only those rows
-  uint64_t atoms_log_ver = ~0ull, last_atoms_ver = ~0ull;
-  std::vector<int32_t> atoms_log;
-  uint64_t host_atoms_ver = ~0ull, dev_atoms_ver = ~0ull;
-  // the work list by cost (sr_ctx::list_cost): the candidate generation whose
-  // K2 durations were copied back (h_cycles, complete at ev_cost), and the one
-  // the list was reordered for
-  uint64_t cost_gen = ~0ull, list_sorted_gen = ~0ull;
-  HostBuf h_cycles;
+  DevBuf tables;      // S and T rows (K0 writes, K2 reads)
+  HostBuf h_cycles;   // the K2 durations of the work list by cost (complete at ev_cost)
   hipEvent_t ev_cost = nullptr;
-  // spot nodes changed since tables_state_gen (valid: every state step since was one the encoder patched)
-  std::vector<int32_t> dirty;
-  bool dirty_valid = false;
-  uint64_t seen_gen = ~0ull;        // encoder state at the slot's last prepare
-  std::vector<int32_t> pending;     // pods re-pointed since the last K0 run (their device records are older)
-  std::vector<uint8_t> pending_mark;
-  bool class_flip = false;          // ... some of them to or from the empty class
-  // what the next K0 launch of this slot brings the tables and the node section to (run() commits it)
-  bool commit_k0 = false;
-  bool need_k0 = true;              // the device records name rows no K0 run has written yet
-  uint64_t key = 0;                 // fingerprint of the input it was last prepared for
-  uint64_t used = 0;                // clock of its last prepare (least recently used is replaced)
+  uint64_t key = 0;   // fingerprint of the input it was last prepared for
+  uint64_t used = 0;  // clock of its last prepare (least recently used is replaced)
 };
 
 }  // namespace
@@ -134,9 +106,8 @@ struct sr_ctx {
   int32_t n_slots = 4;
   Slot* cur = nullptr;       // the slot of the last prepare
   uint64_t slot_clock = 0;
-  std::vector<uint64_t> node_patch_words;  // this call's node patches (prepare)
-  std::vector<int32_t> k0_cols, k0_rows;   // this call's incremental K0 (prepare)
-  std::vector<uint64_t> pod_patch_words;   // this call's pod patches (prepare)
+  sr::TickLists lists;  // this call's patches, K0 lists and copies (prepare)
+  sr::TickPlan plan;    // ... and its decisions
   int32_t k0_incremental = 1;  // SR_K0_INCREMENTAL=0: K0 always rewrites every row
   int32_t k0_skip = 1;         // SR_K0_SKIP=0: every run launches K0
   // SR_K2_SPLIT=0: one K2 launch.  Otherwise a work list the encoder split
@@ -266,33 +237,6 @@ hipError_t host_reserve(HostBuf& b, size_t bytes) {
 // Run tags of every context of the process: a tag is never reused while the
 // process lives (2^32 runs), so words a freed context left behind cannot match.
 std::atomic<uint32_t> g_run_seq{0};
-
-// Packs host vectors into one contiguous staging buffer (256-B aligned
-// sections) so the whole workload goes up in a single copy.
-class Packer {
- public:
-  template <class T>
-  size_t add(const std::vector<T>& v) {
-    size_t off = (size_ + 255) & ~size_t(255);
-    items_.push_back({off, v.data(), v.size() * sizeof(T)});
-    size_ = off + v.size() * sizeof(T);
-    return off;
-  }
-  size_t size() const { return (size_ + 255) & ~size_t(255); }
-  void copy_to(char* dst, size_t from = 0) const {  // the sections at or after `from`
-    for (const auto& it : items_)
-      if (it.bytes && it.off >= from) std::memcpy(dst + it.off, it.src, it.bytes);
-  }
-
- private:
-  struct Item {
-    size_t off;
-    const void* src;
-    size_t bytes;
-  };
-  std::vector<Item> items_;
-  size_t size_ = 0;
-};
 
 // A run may return while K2 still plans the candidates after the winner (the
 // stream keeps later work in order); host-side reallocation of its buffers
@@ -536,213 +480,63 @@ Slot& pick_slot(sr_ctx* ctx, const sr_candidates* cands) {
   return *pick;
 }
 
-sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, const sr_candidates* cands) {
-  auto t0 = std::chrono::steady_clock::now();
-  ctx->prepared = false;
-  if (ctx->shm.host) {  // the walk finds global index g on rank g % N: interleaved shards only
-    const int32_t n = cands->n_cand, N = ctx->nranks;
-    if (n > ctx->shm.max_cand) {
-      ctx->err = "more candidates than sr_comm_init_shm's max_cand";
-      return SR_ERR_CAPACITY;
-    }
-    const int32_t* G = cands->cand_global;
-    if (n > 0 && !G && N > 1) {
-      ctx->err = "the shared-memory transport needs cand_global (interleaved shards)";
+// The shared-memory walk finds global index g on rank g % N: interleaved shards only.
+sr_status check_shm_shards(sr_ctx* ctx, const sr_candidates* cands) {
+  const int32_t n = cands->n_cand, N = ctx->nranks;
+  if (n > ctx->shm.max_cand) {
+    ctx->err = "more candidates than sr_comm_init_shm's max_cand";
+    return SR_ERR_CAPACITY;
+  }
+  const int32_t* G = cands->cand_global;
+  if (n > 0 && !G && N > 1) {
+    ctx->err = "the shared-memory transport needs cand_global (interleaved shards)";
+    return SR_ERR_INVALID_ARG;
+  }
+  const int64_t b = n > 0 && G ? G[0] / N : 0;
+  for (int32_t i = 0; i < n; ++i)
+    if ((G ? G[i] : i) != (b + i) * N + ctx->rank) {
+      ctx->err = "the shared-memory transport needs interleaved shards: cand_global[i] = (first + i) * nranks + rank";
       return SR_ERR_INVALID_ARG;
     }
-    const int64_t b = n > 0 && G ? G[0] / N : 0;
-    for (int32_t i = 0; i < n; ++i)
-      if ((G ? G[i] : i) != (b + i) * N + ctx->rank) {
-        ctx->err = "the shared-memory transport needs interleaved shards: cand_global[i] = (first + i) * nranks + rank";
-        return SR_ERR_INVALID_ARG;
-      }
-    ctx->shm.base = n > 0 ? static_cast<int32_t>(b) : -1;
-  }
-  Slot& sl = pick_slot(ctx, cands);
-  ctx->cur = &sl;
-  sr::Workload& w = sl.wl;
-  std::string err;
-  sr_status st = sr::encode_workload(&ctx->enc, snap, c, cands, &w, &err);
-  if (st != SR_OK) {
-    ctx->err = err;
-    sl.dev_state_gen = ~0ull;  // the encoder may have moved on: upload the node records again
-    return st;
-  }
+  ctx->shm.base = n > 0 ? static_cast<int32_t>(b) : -1;
+  return SR_OK;
+}
+
+sr::ResidencySwitches switches(const sr_ctx* ctx) {
+  sr::ResidencySwitches sw;
+  sw.k0_skip = ctx->k0_skip;
+  sw.k0_incremental = ctx->k0_incremental;
+  sw.node_patch = ctx->node_patch;
+  sw.list_cost = ctx->list_cost;
+  sw.k2_mode = ctx->k2_mode;
+  return sw;
+}
+
+// A reused workload's list in the order of its last run's K2 durations.
+sr_status reorder_list(sr_ctx* ctx, Slot& sl) {
+  HIP_TRY(ctx, hipEventSynchronize(sl.ev_cost));
+  sr::reorder_list_by_cost(sl.wl, static_cast<const uint32_t*>(sl.h_cycles.p), ctx->enc.list_head, ctx->k2_coop);
+  return SR_OK;
+}
+
+// The slot's arenas and tables and the context's output buffers, sized for
+// this call; moved[0..2]: the staging, arena or tables allocation is a new one.
+sr_status reserve_buffers(sr_ctx* ctx, Slot& sl, size_t arena_bytes, bool moved[3]) {
+  const sr::Workload& w = sl.wl;
   const int32_t na = static_cast<int32_t>(w.pod_src.size());
   const int32_t ncand = static_cast<int32_t>(w.cand_global.size());
-  // Arena: the spot nodes' records and free values first (uploaded only when
-  // the encoder's state view changed), then this call's sections.
-  const sr::EncoderCache& E = ctx->enc;
-  // Arena: the node section (spot nodes' records and free values), the
-  // candidate section (class programs, pod records, candidate lists, domain
-  // path and extension records: one candidate generation, w.cand_gen), then
-  // this call's tick section (atoms, thresholds, patches).  Sections the
-  // device already holds are not copied again.
-  Packer pk;
-  const size_t o_nr = pk.add(E.node_rec);
-  const size_t o_nf = pk.add(E.node_free);
-  const size_t node_bytes = pk.size();
-  const size_t o_cpo = pk.add(w.cls_prog_off), o_cp = pk.add(w.cls_prog), o_cp8 = pk.add(w.cls_prog8);
-  const size_t o_prec = pk.add(w.pod_rec);
-  const size_t o_co = pk.add(w.cand_off), o_cg = pk.add(w.cand_global);
-  const size_t o_ls = pk.add(w.list);
-  const bool dyn = !w.dyn_cand.empty();
-  const size_t o_dc = dyn ? pk.add(w.dyn_cand) : 0, o_dp = dyn ? pk.add(w.dyn_pod) : 0;
-  const size_t o_di = dyn ? pk.add(w.ds_info) : 0;
-  const bool ext = !w.ext_cand.empty();
-  const size_t o_ec = ext ? pk.add(w.ext_cand) : 0, o_ep = ext ? pk.add(w.pod_ext) : 0;
-  const size_t o_le = ext ? pk.add(w.list_ext) : 0;
-  // the tick section: the atoms (rows a reuse encode changed go up alone),
-  // then what follows the spot nodes' state every tick
-  const size_t o_at = pk.add(w.atoms);
-  const size_t tick_rest = pk.size();
-  const size_t o_ns = ext ? pk.add(w.node_scal) : 0;  // the spot nodes' scalar usage
-  const size_t o_st = dyn ? pk.add(w.sp_tab) : 0;     // the domain path's base counts
-  const size_t o_dd = dyn ? pk.add(w.dk_dom) : 0;     // ... and node domains (the spot order may move)
-  const size_t o_tt = pk.add(w.t_thr);
-  // the atom-row log (see Slot)
-  if (w.atoms_ver != sl.last_atoms_ver) {
-    const bool follows = w.reused && !w.atom_rows_all && w.atoms_prev_ver == sl.last_atoms_ver;
-    if (follows && sl.atoms_log_ver != ~0ull) {
-      sl.atoms_log.insert(sl.atoms_log.end(), w.atom_rows.begin(), w.atom_rows.end());
-    } else if (follows) {
-      sl.atoms_log_ver = sl.last_atoms_ver;
-      sl.atoms_log = w.atom_rows;
-    } else {
-      sl.atoms_log_ver = ~0ull;
-      sl.atoms_log.clear();
-    }
-    if (sl.atoms_log.size() > 256) {
-      sl.atoms_log_ver = ~0ull;
-      sl.atoms_log.clear();
-    }
-    sl.last_atoms_ver = w.atoms_ver;
-  }
-  if (!w.reused || sl.dev_cand_gen != w.cand_gen) sl.atom_cols.clear();
-  else sl.atom_cols.insert(sl.atom_cols.end(), w.atom_cols.begin(), w.atom_cols.end());
-  // ---- the slot's device state against this call.  Spot nodes changed since
-  // the slot's tables were written, accumulated over K0-less runs:
-  if (w.state_gen != sl.seen_gen) {
-    if (sl.dirty_valid && E.patched_from != ~0ull && E.patched_from == sl.seen_gen && E.state_gen == w.state_gen) {
-      for (int32_t i : E.patched_nodes)
-        if (std::find(sl.dirty.begin(), sl.dirty.end(), i) == sl.dirty.end()) sl.dirty.push_back(i);
-    } else {
-      sl.dirty_valid = false;
-    }
-    sl.seen_gen = w.state_gen;
-  }
-  constexpr size_t kDirtyMax = 64;
-  if (sl.dirty.size() > kDirtyMax) sl.dirty_valid = false;
-  // pods the encoder re-pointed since the last K0 run of this candidate generation
-  if (!w.reused || sl.dev_cand_gen != w.cand_gen) {
-    sl.pending.clear();
-    sl.pending_mark.assign(static_cast<size_t>(na), 0);
-    sl.class_flip = false;
-  } else {
-    if (sl.pending_mark.size() != static_cast<size_t>(na)) sl.pending_mark.assign(static_cast<size_t>(na), 0);
-    for (size_t i = 0; i < w.pod_patch.size(); i += sr::kPodPatchWords) {
-      const int32_t q = static_cast<int32_t>(w.pod_patch[i]);
-      if (!sl.pending_mark[q]) {
-        sl.pending_mark[q] = 1;
-        sl.pending.push_back(q);
-      }
-    }
-    sl.class_flip = sl.class_flip || w.class_flip;
-  }
-  const bool tables_cur = w.reused && sl.tables_cand_gen == w.cand_gen && sl.dev_cand_gen == w.cand_gen &&
-                          sl.tables_thr.size() == w.t_thr.size() && sl.dirty_valid;
-  // A K0-less run: the tables stand for every node but the changed ones, whose
-  // records and T bits K2 takes from the node patches; the atoms (S rows) must
-  // be the tables' and no pod may have left the empty class (K2's dead-pod
-  // shortcut reads the device records).  Node-order candidates only.
-  constexpr size_t kSkipDirty = 16;
-  const bool k0_skip = ctx->k0_skip && ncand > 0 && tables_cur && sl.dirty.size() <= kSkipDirty && !sl.class_flip &&
-                       w.dyn_cand.empty() && w.max_cand_pods <= 256 && ctx->k2_mode == 0 &&
-                       sl.tables_atoms_ver == w.atoms_ver;
-  // node patches {node, node_rec[8], node_free[3]}: the changed nodes' records
-  // ride in the call's copy; K0 writes them into the node section (or K2 reads
-  // them, K0-less)
-  constexpr size_t kPatchNodes = 16;
-  std::vector<uint64_t>& patch = ctx->node_patch_words;
-  patch.clear();
-  if (sl.dirty_valid && !sl.dirty.empty() && sl.dirty.size() <= kPatchNodes) {  // a superset of the nodes the
-                                                                                 // device section lacks
-    const size_t NP = static_cast<size_t>(w.n_pad);
-    for (int32_t i : sl.dirty) {
-      patch.push_back(static_cast<uint64_t>(i));
-      for (size_t j = 0; j < 8; ++j) patch.push_back(E.node_rec[static_cast<size_t>(i) * 8 + j]);
-      for (size_t dm = 0; dm < 3; ++dm) patch.push_back(static_cast<uint64_t>(E.node_free[dm * NP + i]));
-    }
-  }
-  const size_t o_np = patch.empty() ? 0 : pk.add(patch);
-  // pod patches of a K0 run: every pod re-pointed since the last one
-  std::vector<uint64_t>& ppatch = ctx->pod_patch_words;
-  ppatch.clear();
-  if (w.reused && sl.dev_cand_gen == w.cand_gen)  // (unused if the run turns out K0-less)
-    for (int32_t q : sl.pending)
-      ppatch.insert(ppatch.end(), {static_cast<uint64_t>(q), w.pod_rec[static_cast<size_t>(q) * 6 + 4],
-                                   w.pod_rec[static_cast<size_t>(q) * 6 + 5]});
-  const size_t o_pp = ppatch.empty() ? 0 : pk.add(ppatch);
-  // Incremental K0: the tables hold this candidate generation: the word
-  // columns of the changed nodes and the T rows whose threshold moved are
-  // rewritten; anything else rewrites every row.
-  std::vector<int32_t>& kcols = ctx->k0_cols;
-  std::vector<int32_t>& krows = ctx->k0_rows;
-  kcols.clear();
-  krows.clear();
-  bool k0_inc = ctx->k0_incremental && tables_cur;  // (unused if the run turns out K0-less)
-  if (k0_inc) {
-    for (int32_t i : sl.dirty) kcols.push_back(i >> 6);
-    kcols.insert(kcols.end(), sl.atom_cols.begin(), sl.atom_cols.end());
-    std::sort(kcols.begin(), kcols.end());
-    kcols.erase(std::unique(kcols.begin(), kcols.end()), kcols.end());
-    for (size_t r = 0; r < w.t_thr.size(); ++r)
-      if (w.t_thr[r] != sl.tables_thr[r] && w.t_thr[r] != sr::kTSpare) krows.push_back(static_cast<int32_t>(r));
-    if (kcols.size() > 32 || krows.size() > 256) k0_inc = false;
-  }
-  if (!k0_inc) kcols.clear(), krows.clear();
-  const size_t o_kc = kcols.empty() ? 0 : pk.add(kcols), o_kr = krows.empty() ? 0 : pk.add(krows);
-  const size_t bytes = pk.size();
-
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  st = settle(ctx);
-  if (st != SR_OK) return st;
-  // a reused workload's list in the order of its last run's K2 durations
-  // (list_sorted_gen is set once the reordered list's copies are queued: a
-  // prepare failing in between reorders and uploads it again next time)
-  bool list_moved = false;
-  if (ctx->list_cost && w.reused && sl.cost_gen == w.cand_gen && sl.list_sorted_gen != w.cand_gen) {
-    HIP_TRY(ctx, hipEventSynchronize(sl.ev_cost));
-    sr::reorder_list_by_cost(w, static_cast<const uint32_t*>(sl.h_cycles.p), ctx->enc.list_head, ctx->k2_coop);
-    list_moved = true;
-  }
   if (ctx->ev_upload) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_upload));  // staging buffer free again
   const size_t h_cap = sl.h_arena.cap;
-  HIP_TRY(ctx, host_reserve(sl.h_arena, bytes));
-  if (sl.h_arena.cap != h_cap) sl.host_state_gen = sl.host_cand_gen = sl.host_atoms_ver = ~0ull;  // holds none
+  HIP_TRY(ctx, host_reserve(sl.h_arena, arena_bytes));
+  moved[0] = sl.h_arena.cap != h_cap;
   const size_t arena_cap = sl.arena.cap;
-  HIP_TRY(ctx, dev_reserve(sl.arena, bytes));  // a new allocation holds no node records
-  const bool same_arena = sl.arena.cap == arena_cap;
-  if (!same_arena) sl.dev_atoms_ver = ~0ull;
-  const bool nodes_resident = same_arena && sl.dev_state_gen == w.state_gen;
-  // a reuse encode's candidate section is on the device: K0 re-points the
-  // records that moved (a K0-less run reads them as they are)
-  const bool cand_resident = w.reused && same_arena && sl.dev_cand_gen == w.cand_gen;
-  bool skip = k0_skip && cand_resident && same_arena && !sl.need_k0;
-  // a few nodes changed since the generation on the device: K0 applies their
-  // records from this call's copy (K0-less: K2 reads them there)
-  const bool nodes_patch = !nodes_resident && same_arena && !patch.empty() && ctx->node_patch;
+  HIP_TRY(ctx, dev_reserve(sl.arena, arena_bytes));  // a new allocation holds no node records
+  moved[1] = sl.arena.cap != arena_cap;
   const size_t n_rows = static_cast<size_t>(w.n_classes) + w.t_dim.size();
   const size_t row_bytes = static_cast<size_t>(w.Wp) * sizeof(uint64_t);
   const size_t t_cap = sl.tables.cap;
   HIP_TRY(ctx, dev_reserve(sl.tables, n_rows * row_bytes));
-  if (sl.tables.cap != t_cap) {  // a new allocation holds no rows: every row below
-    sl.tables_cand_gen = ~0ull;
-    skip = false;
-    k0_inc = false;
-    kcols.clear();
-    krows.clear();
-  }
+  moved[2] = sl.tables.cap != t_cap;
   HIP_TRY(ctx, dev_reserve(ctx->out_node, sizeof(int32_t) * std::max(1, na)));
   HIP_TRY(ctx, dev_reserve(ctx->out_status, sizeof(int32_t) * std::max(1, ncand)));
   HIP_TRY(ctx, dev_reserve(ctx->out_bytes, sizeof(uint32_t) * std::max(1, ncand)));
@@ -750,149 +544,70 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   const size_t res_bytes = sizeof(uint64_t) * (sr::kResultHeader + static_cast<size_t>(std::max(1, w.max_cand_pods)));
   HIP_TRY(ctx, host_reserve(ctx->h_result, res_bytes));  // mapped: K3 writes the result straight to the host
   HIP_TRY(ctx, host_reserve(ctx->h_early, sizeof(uint64_t) * (static_cast<size_t>(ncand) + na + 1)));
-  auto t1 = std::chrono::steady_clock::now();
-  const size_t from = nodes_resident || nodes_patch ? node_bytes : 0;
-  // The staging arena keeps the node section of the generation it last held:
-  // when that is the current one, or the one the encoder patched a few nodes
-  // on, only those nodes' records are rewritten (no copy of the whole section).
-  {
-    char* hs = static_cast<char*>(sl.h_arena.p);
-    const size_t NP = static_cast<size_t>(w.n_pad);
-    if (sl.host_state_gen == w.state_gen) {
-      // current
-    } else if (E.patched_from != ~0ull && sl.host_state_gen == E.patched_from && E.state_gen == w.state_gen &&
-               !E.patched_nodes.empty()) {
-      for (int32_t i : E.patched_nodes) {
-        std::memcpy(hs + o_nr + static_cast<size_t>(i) * 64, &E.node_rec[static_cast<size_t>(i) * 8], 64);
-        for (size_t dm = 0; dm < 3; ++dm)
-          std::memcpy(hs + o_nf + (dm * NP + static_cast<size_t>(i)) * 8, &E.node_free[dm * NP + i], 8);
-      }
-    } else {
-      std::memcpy(hs + o_nr, E.node_rec.data(), E.node_rec.size() * sizeof(uint64_t));
-      std::memcpy(hs + o_nf, E.node_free.data(), E.node_free.size() * sizeof(int64_t));
-    }
-    sl.host_state_gen = w.state_gen;
-  }
-  // the candidate section: kept in staging across a reuse encode (its pod
-  // patches applied there too), packed again otherwise
-  char* hs = static_cast<char*>(sl.h_arena.p);
-  const size_t row_bytes8 = static_cast<size_t>(w.Wp) * sizeof(uint64_t);
-  auto log_rows = [&](uint64_t have) {  // the rows a copy of version `have` lacks (null: every row)
-    return have == w.atoms_ver ? &sl.atoms_log  // (unused)
-           : sl.atoms_log_ver != ~0ull && have == sl.atoms_log_ver ? &sl.atoms_log : nullptr;
-  };
-  if (w.reused && sl.host_cand_gen == w.cand_gen) {
-    for (size_t i = 0; i < w.pod_patch.size(); i += sr::kPodPatchWords)
-      std::memcpy(hs + o_prec + (static_cast<size_t>(w.pod_patch[i]) * 6 + 4) * 8, &w.pod_patch[i + 1], 16);
-    if (sl.host_atoms_ver != w.atoms_ver) {
-      const std::vector<int32_t>* rows = log_rows(sl.host_atoms_ver);
-      if (rows) {
-        for (int32_t r : *rows)
-          std::memcpy(hs + o_at + static_cast<size_t>(r) * row_bytes8, w.atoms.data() + static_cast<size_t>(r) * w.Wp, row_bytes8);
-      } else {
-        std::memcpy(hs + o_at, w.atoms.data(), w.atoms.size() * sizeof(uint64_t));
-      }
-    }
-    if (list_moved) {
-      std::memcpy(hs + o_ls, w.list.data(), w.list.size() * sizeof(int32_t));
-      if (ext) std::memcpy(hs + o_le, w.list_ext.data(), w.list_ext.size() * sizeof(int32_t));
-    }
-    pk.copy_to(hs, tick_rest);
-  } else {
-    pk.copy_to(hs, node_bytes);
-  }
-  sl.host_cand_gen = w.cand_gen;
-  sl.host_atoms_ver = w.atoms_ver;
-  if (!cand_resident) {  // the records go up whole, current: nothing pending, but rows to write
-    sl.pending.clear();
-    std::fill(sl.pending_mark.begin(), sl.pending_mark.end(), 0);
-    sl.class_flip = false;
-    sl.need_k0 = true;
-  }
-  char* dv = static_cast<char*>(sl.arena.p);
-  size_t atoms_up = tick_rest - o_at;  // atom bytes uploaded
-  if (!cand_resident) {
-    HIP_TRY(ctx, hipMemcpyAsync(dv + from, hs + from, bytes - from, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    if (from < node_bytes)
-      HIP_TRY(ctx, hipMemcpyAsync(dv, hs, node_bytes, hipMemcpyHostToDevice, ctx->stream));
-    // the atoms: current, a few rows behind (each row alone), or whole
-    const std::vector<int32_t>* rows = sl.dev_atoms_ver == w.atoms_ver ? nullptr : log_rows(sl.dev_atoms_ver);
-    if (sl.dev_atoms_ver == w.atoms_ver) {
-      atoms_up = 0;
-    } else if (rows && rows->size() <= 32) {
-      for (int32_t r : *rows) {
-        const size_t o = o_at + static_cast<size_t>(r) * row_bytes8;
-        HIP_TRY(ctx, hipMemcpyAsync(dv + o, hs + o, row_bytes8, hipMemcpyHostToDevice, ctx->stream));
-      }
-      atoms_up = rows->size() * row_bytes8;
-    } else {
-      HIP_TRY(ctx, hipMemcpyAsync(dv + o_at, hs + o_at, tick_rest - o_at, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(dv + tick_rest, hs + tick_rest, bytes - tick_rest, hipMemcpyHostToDevice, ctx->stream));
-    if (list_moved) {  // the reordered work list into the resident candidate section
-      HIP_TRY(ctx, hipMemcpyAsync(dv + o_ls, hs + o_ls, w.list.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                  ctx->stream));
-      if (ext)
-        HIP_TRY(ctx, hipMemcpyAsync(dv + o_le, hs + o_le, w.list_ext.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                    ctx->stream));
-    }
-  }
-  sl.dev_atoms_ver = w.atoms_ver;
-  if (sl.host_atoms_ver == w.atoms_ver) {  // both copies current: the log starts again here
-    sl.atoms_log_ver = w.atoms_ver;
-    sl.atoms_log.clear();
-  }
-  if (!ctx->ev_upload) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));  // kernels queue behind the copy
-  if (!nodes_patch) sl.dev_state_gen = w.state_gen;  // the section went up whole (or was current)
-  sl.dev_cand_gen = w.cand_gen;
-  if (list_moved) sl.list_sorted_gen = w.cand_gen;
-  ctx->t.k2_list_by_cost = sl.list_sorted_gen == w.cand_gen ? 1 : 0;
-  // run() commits what a K0 launch brings the slot to
-  sl.commit_k0 = !skip;
-  auto t2 = std::chrono::steady_clock::now();
+  return SR_OK;
+}
 
+// The copies resolve() listed, then ev_upload: kernels queue behind them.
+sr_status queue_upload(sr_ctx* ctx, Slot& sl) {
+  const char* hs = static_cast<const char*>(sl.h_arena.p);
+  char* dv = static_cast<char*>(sl.arena.p);
+  for (const sr::ArenaCopy& c : ctx->lists.copies)
+    HIP_TRY(ctx, hipMemcpyAsync(dv + c.off, hs + c.off, c.bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (!ctx->ev_upload) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
+  return SR_OK;
+}
+
+// The kernels' view of the prepared workload: pointers into the slot's arena
+// by the tick's layout, the lists and switches the tick decided on.
+sr_status fill_dev_workload(sr_ctx* ctx, Slot& sl) {
+  const sr::Workload& w = sl.wl;
+  const sr::TickPlan& p = ctx->plan;
+  const sr::ArenaLayout& o = p.at;
+  const sr::TickLists& tl = ctx->lists;
+  const int32_t na = static_cast<int32_t>(w.pod_src.size());
+  const int32_t ncand = static_cast<int32_t>(w.cand_global.size());
   char* base = static_cast<char*>(sl.arena.p);
   auto at = [base](size_t off) { return static_cast<void*>(base + off); };
+  const bool dyn = o.dyn, ext = o.ext;
   sr::DevWorkload& d = ctx->dw;
   d = sr::DevWorkload{};
   d.n_spot = w.n_spot;
   d.n_pad = w.n_pad;
   d.Wp = w.Wp;
-  d.node_rec = static_cast<const uint64_t*>(at(o_nr));
-  d.node_free = static_cast<const int64_t*>(at(o_nf));
+  d.node_rec = static_cast<const uint64_t*>(at(o.node_rec));
+  d.node_free = static_cast<const int64_t*>(at(o.node_free));
   d.n_atoms = w.n_atoms;
-  d.atoms = static_cast<const uint64_t*>(at(o_at));
-  d.cls_prog_off = static_cast<const int32_t*>(at(o_cpo));
-  d.cls_prog = static_cast<const int32_t*>(at(o_cp));
-  d.cls_prog8 = static_cast<const int32_t*>(at(o_cp8));
+  d.atoms = static_cast<const uint64_t*>(at(o.atoms));
+  d.cls_prog_off = static_cast<const int32_t*>(at(o.cls_prog_off));
+  d.cls_prog = static_cast<const int32_t*>(at(o.cls_prog));
+  d.cls_prog8 = static_cast<const int32_t*>(at(o.cls_prog8));
   d.n_classes = w.n_classes;
   d.s_empty_off = w.empty_class >= 0 ? static_cast<uint32_t>(w.empty_class) * static_cast<uint32_t>(w.Wp) : 0xffffffffu;
   d.n_t = static_cast<int32_t>(w.t_dim.size());
   for (int i = 0; i < 5; ++i) d.t_off[i] = w.t_off[i];
-  d.t_thr = static_cast<const int64_t*>(at(o_tt));
+  d.t_thr = static_cast<const int64_t*>(at(o.t_thr));
   d.n_pods = na;
-  d.pod_rec = static_cast<const uint64_t*>(at(o_prec));
+  d.pod_rec = static_cast<const uint64_t*>(at(o.pod_rec));
   d.n_cand = ncand;
-  d.cand_off = static_cast<const int32_t*>(at(o_co));
-  d.cand_global = static_cast<const int32_t*>(at(o_cg));
-  d.list = static_cast<const int4*>(at(o_ls));
+  d.cand_off = static_cast<const int32_t*>(at(o.cand_off));
+  d.cand_global = static_cast<const int32_t*>(at(o.cand_global));
+  d.list = static_cast<const int4*>(at(o.list));
   d.n_list = static_cast<int32_t>(w.list.size() / 4);
   d.n_list_head = std::min(d.n_list, sr::kListInline);
   for (int32_t i = 0; i < d.n_list_head; ++i)
     d.list_head[i] = int4{w.list[4 * i], w.list[4 * i + 1], w.list[4 * i + 2], w.list[4 * i + 3]};
   d.max_np = w.max_cand_pods;
-  d.dyn_cand = dyn ? static_cast<const int32_t*>(at(o_dc)) : nullptr;
-  d.dyn_pod = dyn ? static_cast<const uint64_t*>(at(o_dp)) : nullptr;
-  d.dk_dom = dyn ? static_cast<const int32_t*>(at(o_dd)) : nullptr;
-  d.ds_info = dyn ? static_cast<const int32_t*>(at(o_di)) : nullptr;
-  d.sp_tab = dyn ? static_cast<const int32_t*>(at(o_st)) : nullptr;
+  d.dyn_cand = dyn ? static_cast<const int32_t*>(at(o.dyn_cand)) : nullptr;
+  d.dyn_pod = dyn ? static_cast<const uint64_t*>(at(o.dyn_pod)) : nullptr;
+  d.dk_dom = dyn ? static_cast<const int32_t*>(at(o.dk_dom)) : nullptr;
+  d.ds_info = dyn ? static_cast<const int32_t*>(at(o.ds_info)) : nullptr;
+  d.sp_tab = dyn ? static_cast<const int32_t*>(at(o.sp_tab)) : nullptr;
   d.n_dk = w.n_dk;
-  d.ext_cand = ext ? static_cast<const int32_t*>(at(o_ec)) : nullptr;
-  d.pod_ext = ext ? static_cast<const uint64_t*>(at(o_ep)) : nullptr;
-  d.list_ext = ext ? static_cast<const int4*>(at(o_le)) : nullptr;
-  d.node_scal = ext ? static_cast<const int64_t*>(at(o_ns)) : nullptr;
+  d.ext_cand = ext ? static_cast<const int32_t*>(at(o.ext_cand)) : nullptr;
+  d.pod_ext = ext ? static_cast<const uint64_t*>(at(o.pod_ext)) : nullptr;
+  d.list_ext = ext ? static_cast<const int4*>(at(o.list_ext)) : nullptr;
+  d.node_scal = ext ? static_cast<const int64_t*>(at(o.node_scal)) : nullptr;
   static_assert(sr::kDevExtU64 == sr::kExtU64, "extension record layout shared by encode.cpp and kernels.hip");
   static_assert(sr::kDevDynU64 == sr::kDynU64 && sr::kDevDomKeys == sr::kDomKeys && sr::kDevDynTerms == sr::kDynTerms &&
                     sr::kDevSpreadSlots == sr::kSpreadSlots,
@@ -910,12 +625,11 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   d.k2_wpb = ctx->k2_wpb;
   d.k2_excl = ctx->k2_excl;
   d.k2_node_kernel = ctx->k2_node_kernel;
-  // Wide rows, every candidate on the node-order kernel (launch_k2's condition)
-  // and every class program in its 8-slot record: K0 writes only the S-row
-  // heads, K2 evaluates S words beyond them from the programs.
+  // Wide rows, every candidate on the node-order kernel and every class
+  // program in its 8-slot record: K0 writes only the S-row heads, K2
+  // evaluates S words beyond them from the programs.
   d.s_head_only = 0;
-  if (ctx->s_head_only && w.Wp > 64 && w.dyn_cand.empty() && ctx->k2_mode == 0 && ctx->k2_node_kernel &&
-      w.max_cand_pods >= 1 && w.max_cand_pods <= 256) {
+  if (ctx->s_head_only && w.Wp > 64 && sr::k2_node_launch(dyn, ctx->k2_mode, w.max_cand_pods, ctx->k2_node_kernel)) {
     bool short_programs = true;
     for (int32_t k = 0; k < w.n_classes && short_programs; ++k)
       short_programs = w.cls_prog8[static_cast<size_t>(k) * 8] != -2;
@@ -936,37 +650,37 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   HIP_TRY(ctx, hipHostGetDevicePointer(&dres, ctx->h_early.p, 0));
   ctx->d_early = static_cast<uint64_t*>(dres);
   d.res_stat = d.res_map = nullptr;  // set per run
-  ctx->t.bytes_uploaded = static_cast<uint64_t>(cand_resident ? (from < node_bytes ? node_bytes : 0) + atoms_up +
-                                                                   bytes - tick_rest
-                                                               : bytes - from);
-  // K0 writes the patches into the node section; a K0-less run's K2 reads them
-  // (every changed node, whether or not the section went up whole)
-  const bool use_patch = skip ? !patch.empty() : nodes_patch;
-  d.node_patch = use_patch ? static_cast<const uint64_t*>(at(o_np)) : nullptr;
-  d.n_node_patch = use_patch ? static_cast<int32_t>(patch.size() / sr::kNodePatchU64) : 0;
-  if (skip) k0_inc = false;
-  d.k0_inc = k0_inc ? 1 : 0;
-  d.n_k0_cols = static_cast<int32_t>(kcols.size());
-  d.n_k0_rows = static_cast<int32_t>(krows.size());
-  d.k0_cols = kcols.empty() ? nullptr : static_cast<const int32_t*>(at(o_kc));
-  d.k0_rows = krows.empty() ? nullptr : static_cast<const int32_t*>(at(o_kr));
-  const bool pods_patch = !skip && cand_resident && !ppatch.empty();
-  d.pod_patch = pods_patch ? static_cast<const uint64_t*>(at(o_pp)) : nullptr;
-  d.n_pod_patch = pods_patch ? static_cast<int32_t>(ppatch.size() / sr::kPodPatchU64) : 0;
-  d.k0_skip = skip ? 1 : 0;
-  d.n_dirty = 0;
-  if (skip) {  // the changed nodes in the kernel arguments (<= 16: kSkipDirty)
-    const size_t NP = static_cast<size_t>(w.n_pad);
-    for (int32_t i : sl.dirty) {
-      d.dirty_node[d.n_dirty] = i;
-      for (size_t dm = 0; dm < 3; ++dm) d.dirty_free[d.n_dirty][dm] = E.node_free[dm * NP + static_cast<size_t>(i)];
-      ++d.n_dirty;
-    }
+  d.node_patch = p.n_node_patch ? static_cast<const uint64_t*>(at(o.node_patch)) : nullptr;
+  d.n_node_patch = p.n_node_patch;
+  d.k0_inc = p.k0_inc ? 1 : 0;
+  d.n_k0_cols = static_cast<int32_t>(tl.k0_cols.size());
+  d.n_k0_rows = static_cast<int32_t>(tl.k0_rows.size());
+  d.k0_cols = tl.k0_cols.empty() ? nullptr : static_cast<const int32_t*>(at(o.k0_cols));
+  d.k0_rows = tl.k0_rows.empty() ? nullptr : static_cast<const int32_t*>(at(o.k0_rows));
+  d.pod_patch = p.n_pod_patch ? static_cast<const uint64_t*>(at(o.pod_patch)) : nullptr;
+  d.n_pod_patch = p.n_pod_patch;
+  d.k0_skip = p.skip ? 1 : 0;
+  d.n_dirty = p.n_dirty;
+  for (int32_t i = 0; i < p.n_dirty; ++i) {
+    d.dirty_node[i] = p.dirty_node[i];
+    for (int dm = 0; dm < 3; ++dm) d.dirty_free[i][dm] = p.dirty_free[i][dm];
   }
-  static_assert(sizeof(d.dirty_node) / sizeof(d.dirty_node[0]) == 16, "kSkipDirty nodes in the kernel arguments");
+  static_assert(sizeof(d.dirty_node) / sizeof(d.dirty_node[0]) == sr::kSkipDirty, "kSkipDirty nodes in the kernel arguments");
   d.first_fallback_local = w.first_fallback;
-  static_assert(sr::kPodPatchU64 == sr::kPodPatchWords && sr::kTPad == sr::kTSpare, "patch layout shared with encode.cpp");
+  static_assert(sr::kPodPatchU64 == sr::kPodPatchWords && sr::kNodePatchU64 == sr::kNodePatchWords &&
+                    sr::kTPad == sr::kTSpare,
+                "patch layout shared with encode.cpp and residency.cpp");
+  return SR_OK;
+}
 
+// sr_timing of the prepared workload: its dimensions, what the encoder and the
+// upload had to do, and K0's algorithmic bytes.
+void account_prepare(sr_ctx* ctx, const sr::Workload& w, double ms_pack_host, double ms_upload) {
+  const sr::DevWorkload& d = ctx->dw;
+  const sr::TickPlan& p = ctx->plan;
+  const std::vector<int32_t>& kcols = ctx->lists.k0_cols;
+  const std::vector<int32_t>& krows = ctx->lists.k0_rows;
+  ctx->t.bytes_uploaded = p.bytes_uploaded;
   const uint64_t row = static_cast<uint64_t>(w.Wp) * 8;
   // K0 algorithmic bytes: every table row written once; every atom row a class
   // program names, the nodes' free capacities and the thresholds read once.
@@ -974,7 +688,7 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   const uint64_t s_row = d.s_head_only ? static_cast<uint64_t>(std::min(w.Wp, 8)) * 8 : row;  // S words K0 writes
   ctx->t.bytes_tables = static_cast<uint64_t>(w.n_classes) * s_row + w.t_dim.size() * row + atom_reads * s_row +
                         3ull * 8 * w.n_pad + 32ull * w.n_classes;
-  if (k0_inc) {  // the changed columns of every row (S columns inside the written head), the moved rows whole
+  if (p.k0_inc) {  // the changed columns of every row (S columns inside the written head), the moved rows whole
     const int32_t s_words = d.s_head_only ? std::min(w.Wp, 8) : w.Wp;
     uint64_t s_cols = 0;
     for (int32_t col : kcols) s_cols += col < s_words ? 1 : 0;
@@ -987,11 +701,11 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   ctx->t.bytes_placement = 0;
   ctx->issued_known = false;
   ctx->issued_checks = 0;
-  ctx->t.ms_pack_host = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  ctx->t.ms_upload = std::chrono::duration<double, std::milli>(t2 - t1).count();
-  ctx->t.n_pods = na;
+  ctx->t.ms_pack_host = ms_pack_host;
+  ctx->t.ms_upload = ms_upload;
+  ctx->t.n_pods = d.n_pods;
   ctx->t.n_spot = w.n_spot;
-  ctx->t.n_cand = ncand;
+  ctx->t.n_cand = d.n_cand;
   ctx->t.n_words = w.Wp;
   ctx->t.n_rows_static = d.n_classes;
   ctx->t.n_rows_threshold = d.n_t;
@@ -1002,10 +716,53 @@ sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, con
   ctx->t.enc_memo_pods = ctx->enc.last_memo_hits;
   ctx->t.enc_reused = ctx->enc.last_reused;
   ctx->t.enc_pod_patches = ctx->enc.last_pod_patches;
-  ctx->t.k0_columns = skip ? -2 : k0_inc ? static_cast<int32_t>(kcols.size()) : -1;
-  ctx->t.k0_rows_moved = k0_inc ? static_cast<int32_t>(krows.size()) : 0;
-  ctx->t.k0_dirty_nodes = skip ? static_cast<int32_t>(patch.size() / sr::kNodePatchU64) : 0;
-  if (skip) ctx->t.bytes_tables = 0;
+  ctx->t.k0_columns = p.skip ? -2 : p.k0_inc ? static_cast<int32_t>(kcols.size()) : -1;
+  ctx->t.k0_rows_moved = p.k0_inc ? static_cast<int32_t>(krows.size()) : 0;
+  ctx->t.k0_dirty_nodes = p.skip ? static_cast<int32_t>(ctx->lists.node_patch.size() / sr::kNodePatchWords) : 0;
+  if (p.skip) ctx->t.bytes_tables = 0;
+}
+
+sr_status prepare(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* c, const sr_candidates* cands) {
+  using ms = std::chrono::duration<double, std::milli>;
+  auto t0 = std::chrono::steady_clock::now();
+  ctx->prepared = false;
+  sr_status st = ctx->shm.host ? check_shm_shards(ctx, cands) : SR_OK;
+  if (st != SR_OK) return st;
+  Slot& sl = pick_slot(ctx, cands);
+  ctx->cur = &sl;
+  sr::Workload& w = sl.wl;
+  std::string err;
+  st = sr::encode_workload(&ctx->enc, snap, c, cands, &w, &err);
+  if (st != SR_OK) {
+    ctx->err = err;
+    sl.res.encode_failed();
+    return st;
+  }
+  const sr::ResidencySwitches sw = switches(ctx);
+  sr::TickPlan& p = ctx->plan;
+  sl.res.observe(w, ctx->enc, sw, &ctx->lists, &p);
+
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  st = settle(ctx);
+  if (st == SR_OK && p.reorder_due) st = reorder_list(ctx, sl);
+  if (st != SR_OK) return st;
+  bool moved[3] = {false, false, false};
+  st = reserve_buffers(ctx, sl, p.at.bytes, moved);
+  if (st != SR_OK) {
+    sl.res.moved(moved[0], moved[1], moved[2]);  // (the next prepare must not take a new allocation for the old one)
+    return st;
+  }
+  auto t1 = std::chrono::steady_clock::now();
+  sl.res.resolve(w, ctx->enc, sw, moved[0], moved[1], moved[2], p.reorder_due, static_cast<char*>(sl.h_arena.p),
+                 &ctx->lists, &p);
+  st = queue_upload(ctx, sl);
+  if (st != SR_OK) return st;
+  sl.res.upload_queued(w, p);
+  ctx->t.k2_list_by_cost = sl.res.list_by_cost(w) ? 1 : 0;
+  auto t2 = std::chrono::steady_clock::now();
+  st = fill_dev_workload(ctx, sl);
+  if (st != SR_OK) return st;
+  account_prepare(ctx, w, ms(t1 - t0).count(), ms(t2 - t1).count());
   ctx->prepared = true;
   return SR_OK;
 }
@@ -1160,265 +917,210 @@ sr_status finish_sequence(sr_ctx* ctx, SeqWalk* sq) {
   return SR_OK;
 }
 
-sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* sq = nullptr) {
-  if (!ctx->prepared) {
-    ctx->err = "sr_plan_run before sr_plan_prepare";
-    return SR_ERR_STATE;
-  }
-  const sr::Workload& w = ctx->cur->wl;
-  sr::DevWorkload& d = ctx->dw;
-  hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool collective = has_comm(ctx) && use_comm;
-  // Single rank, winner only: K2 writes each candidate's outcome to the host
-  // and the run returns once the candidates up to the winner are known (no K3)
-  const bool early = !collective && !full && (!ctx->prof_file || sq);
-  const int32_t timing = (ctx->timing_runs++ % ctx->timing_every) == 0 ? ctx->timing : 0;
-  ctx->timing_cur = timing;
-  do ctx->seq = g_run_seq.fetch_add(1, std::memory_order_relaxed) + 1;
-  while (ctx->seq == 0);  // tag 0 is never used: fresh result memory holds zeros
-  d.seq = ctx->seq;
-  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
-  // Timed kernels get an event pair from the pool, recorded by their own
-  // dispatch (hipExtLaunchKernelGGL); the collective is bracketed with
-  // plain records.  Events are read back lazily (flush_timing).
-  // k: 0 = K0, 1 = K2, 2 = K3, 3 = the collective (mask bit 2, with K3)
-  auto pair_for = [&](int k, hipEvent_t* a, hipEvent_t* b) -> sr_status {
-    *a = *b = nullptr;
-    if (!(timing >> (k == 3 ? 2 : k) & 1)) return SR_OK;
-    if (ctx->ev_used == ctx->ev_start.size()) {
-      if (ctx->ev_used >= 3072) {  // bounded pool: read back what is pending
-        sr_status st = flush_timing(ctx);
-        if (st != SR_OK) return st;
-      } else {
-        hipEvent_t e0, e1;
-        HIP_TRY(ctx, hipEventCreate(&e0));
-        HIP_TRY(ctx, hipEventCreate(&e1));
-        ctx->ev_start.push_back(e0);
-        ctx->ev_end.push_back(e1);
-        ctx->ev_kernel.push_back(0);
-      }
-    }
-    const size_t i = ctx->ev_used++;
-    ctx->ev_kernel[i] = static_cast<int8_t>(k);
-    *a = ctx->ev_start[i];
-    *b = ctx->ev_end[i];
-    return SR_OK;
-  };
-#define PAIR(k, a, b)                         \
-  hipEvent_t a, b;                            \
-  do {                                        \
-    sr_status _st = pair_for((k), &a, &b);    \
-    if (_st != SR_OK) return _st;             \
+#define SR_TRY(expr)                   \
+  do {                                 \
+    sr_status _st = (expr);            \
+    if (_st != SR_OK) return _st;      \
   } while (0)
-  hipEvent_t e0a = nullptr, e0b = nullptr;  // K0's pair only when it is launched (an unrecorded event fails)
-  if (!d.k0_skip) {
-    sr_status pst = pair_for(0, &e0a, &e0b);
-    if (pst != SR_OK) return pst;
+
+// Timed kernels get an event pair from the pool, recorded by their own
+// dispatch (hipExtLaunchKernelGGL); the collective is bracketed with
+// plain records.  Events are read back lazily (flush_timing).
+// k: 0 = K0, 1 = K2, 2 = K3, 3 = the collective (mask bit 2, with K3);
+// both null when the current run does not time kernel k
+sr_status event_pair(sr_ctx* ctx, int k, hipEvent_t* a, hipEvent_t* b) {
+  *a = *b = nullptr;
+  if (!(ctx->timing_cur >> (k == 3 ? 2 : k) & 1)) return SR_OK;
+  if (ctx->ev_used == ctx->ev_start.size()) {
+    if (ctx->ev_used >= 3072) {  // bounded pool: read back what is pending
+      SR_TRY(flush_timing(ctx));
+    } else {
+      hipEvent_t e0, e1;
+      HIP_TRY(ctx, hipEventCreate(&e0));
+      HIP_TRY(ctx, hipEventCreate(&e1));
+      ctx->ev_start.push_back(e0);
+      ctx->ev_end.push_back(e1);
+      ctx->ev_kernel.push_back(0);
+    }
   }
-  // the first run of a candidate generation records its K2 durations (list_cost)
-  Slot& slc = *ctx->cur;
-  const bool want_cost = ctx->list_cost && d.n_list > ctx->list_cost_min && slc.list_sorted_gen != w.cand_gen &&
-                         slc.cost_gen != w.cand_gen;
-  d.out_cycles = nullptr;
-  if (want_cost) {
-    HIP_TRY(ctx, dev_reserve(ctx->out_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand)));
-    HIP_TRY(ctx, host_reserve(slc.h_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand)));
-    if (!slc.ev_cost) HIP_TRY(ctx, hipEventCreateWithFlags(&slc.ev_cost, hipEventDisableTiming));
-    d.out_cycles = static_cast<uint32_t*>(ctx->out_cycles.p);
-  }
-  // d_min alternates between two buffers: K0 resets this run's, K2 the next's
-  const int par = static_cast<int>(ctx->run_count++ & 1);
-  d.d_min = static_cast<int32_t*>(ctx->dmin.p) + 8 * par;
-  d.d_min_next = static_cast<int32_t*>(ctx->dmin.p) + 8 * (1 - par);
-  Slot& sl = *ctx->cur;
-  // the split launch (see sr_ctx::k2_split): the node-order part on this
-  // stream, the general one on stream2 between a fork and a join event
-  const int32_t n_node = w.n_list_node;
-  const bool split = ctx->k2_split && n_node > 0 && n_node < d.n_list && d.k2_mode == 0 && d.k2_node_kernel &&
-                     w.max_np_node >= 1 && w.max_np_node <= 256;
-  if (split && !ctx->stream2) {
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-  }
-  // the fork is K0's own completion signal when K0 runs untimed (no marker
-  // packet between K0 and K2: ~5 us per marker on the split tick)
-  bool forked = false;
+  const size_t i = ctx->ev_used++;
+  ctx->ev_kernel[i] = static_cast<int8_t>(k);
+  *a = ctx->ev_start[i];
+  *b = ctx->ev_end[i];
+  return SR_OK;
+}
+
+// K0 (with the slot's commit of what it writes), or on a K0-less run the reset
+// of d_min when no K2 of a previous run did it.  forked: K0's dispatch signals
+// the split launch's fork event itself (K0 untimed: no marker packet between
+// K0 and K2, ~5 us per marker on the split tick).
+sr_status queue_tables(sr_ctx* ctx, Slot& sl, bool split, int par, hipEvent_t e0a, hipEvent_t e0b, bool* forked) {
+  const sr::DevWorkload& d = ctx->dw;
+  *forked = false;
   if (d.k0_skip) {
     if (!ctx->dmin_ready[par])  // no K2 of a previous run reset it: reset here
-      HIP_TRY(ctx, hipMemsetAsync(d.d_min, 0xff, sizeof(uint64_t), s));
+      HIP_TRY(ctx, hipMemsetAsync(d.d_min, 0xff, sizeof(uint64_t), ctx->stream));
   } else {
-    forked = split && !e0b && ctx->k2_dispatch_events;
-    HIP_TRY(ctx, sr::launch_tables(d, w.first_fallback, s, e0a, forked ? ctx->ev_fork : e0b));
-    if (sl.commit_k0) {  // K0 wrote the node and pod patches and brought the rows to this workload (a rerun:
-      sl.commit_k0 = false;  // idempotent)
-      sl.tables_cand_gen = w.cand_gen;
-      sl.tables_state_gen = sl.dev_state_gen = w.state_gen;
-      if (sl.tables_thr != w.t_thr) sl.tables_thr = w.t_thr;
-      sl.tables_atoms_ver = w.atoms_ver;
-      sl.atom_cols.clear();
-      sl.dirty.clear();
-      sl.dirty_valid = true;
-      sl.seen_gen = w.state_gen;
-      for (int32_t q : sl.pending) sl.pending_mark[q] = 0;
-      sl.pending.clear();
-      sl.class_flip = false;
-      sl.need_k0 = false;
-    }
+    *forked = split && !e0b && ctx->k2_dispatch_events;
+    HIP_TRY(ctx, sr::launch_tables(d, sl.wl.first_fallback, ctx->stream, e0a, *forked ? ctx->ev_fork : e0b));
+    sl.res.k0_queued(sl.wl);
   }
   ctx->dmin_ready[par] = false;
   ctx->dmin_ready[1 - par] = d.n_list > 0;  // K2's first candidate resets it
-  PAIR(1, e1a, e1b);
-  const bool shm = collective && ctx->shm.host;  // ranks reduce through host memory: no collective, no K3
-  int shm_par = 0;
-  if (early) {
-    d.res_stat = ctx->d_early;
-    d.res_map = ctx->d_early + d.n_cand;
-  } else if (shm) {
-    sr_status pst = shm_publish(ctx, &shm_par);
-    if (pst != SR_OK) return pst;
-  } else {
-    d.res_stat = d.res_map = nullptr;
-  }
+  return SR_OK;
+}
+
+// K2: one launch, or the split launch (see sr_ctx::k2_split): the node-order
+// part on this stream, the general one on stream2 between a fork and a join
+// event.
+sr_status queue_placement(sr_ctx* ctx, Slot& sl, bool split, bool forked, hipEvent_t e1a, hipEvent_t e1b) {
+  const sr::Workload& w = sl.wl;
+  sr::DevWorkload& d = ctx->dw;
+  hipStream_t s = ctx->stream;
+  const int32_t n_node = w.n_list_node;
   ctx->t.k2_launches = d.n_list > 0 ? (split ? 2 : 1) : 0;
   // cooperative blocks for the front of a cost-ordered list, on a node-order
   // launch of four waves per block without extension records
   d.n_coop = 0;
-  {
-    const bool node_launch = split || (!d.dyn_cand && d.k2_mode == 0 && d.max_np >= 1 && d.max_np <= 256 &&
-                                       d.k2_node_kernel);
-    const int32_t len = split ? n_node : d.n_list;
-    const int32_t wpb = d.k2_wpb == 1 || d.k2_wpb == 2 || d.k2_wpb == 4 ? d.k2_wpb : (len <= 2048 ? 1 : 4);
-    if (node_launch && wpb == 4 && !d.ext_cand && ctx->cur->list_sorted_gen == w.cand_gen)
-      d.n_coop = std::min(w.n_coop_front, len);
-  }
+  const bool node_launch = split || sr::k2_node_launch(d.dyn_cand != nullptr, d.k2_mode, d.max_np, d.k2_node_kernel);
+  const int32_t len = split ? n_node : d.n_list;
+  if (node_launch && sr::k2_waves_per_block(d.k2_wpb, len) == 4 && !d.ext_cand && sl.res.list_by_cost(w))
+    d.n_coop = std::min(w.n_coop_front, len);
   ctx->t.k2_coop = d.n_coop;
-  if (split) {
-    sr::DevWorkload dp = d, dn = d;
-    dp.list = d.list + n_node;
-    dp.n_list = d.n_list - n_node;
-    dp.n_list_head = 0;
-    dp.n_coop = 0;  // (the general kernel)
-    if (d.list_ext) dp.list_ext = d.list_ext + n_node;
-    dn.n_list = n_node;
-    dn.n_list_head = std::min(d.n_list_head, n_node);
-    dn.max_np = w.max_np_node;
-    dn.dyn_cand = nullptr;  // none of its candidates is on the domain path
-    if (e1a) HIP_TRY(ctx, hipEventRecord(e1a, s));
-    if (!forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    // the join is the general kernel's own completion signal
-    HIP_TRY(ctx, sr::launch_placement(dp, ctx->stream2, nullptr, ctx->k2_dispatch_events ? ctx->ev_join : nullptr));
-    if (!ctx->k2_dispatch_events) HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    HIP_TRY(ctx, sr::launch_placement(dn, s, nullptr, nullptr));
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-    if (e1b) HIP_TRY(ctx, hipEventRecord(e1b, s));
-  } else {
+  if (!split) {
     HIP_TRY(ctx, sr::launch_placement(d, s, e1a, e1b));
+    return SR_OK;
   }
-  if (want_cost) {  // after K2 in stream order: the next prepare waits for it (ev_cost)
-    HIP_TRY(ctx, hipMemcpyAsync(slc.h_cycles.p, d.out_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand),
-                                hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipEventRecord(slc.ev_cost, s));
-    slc.cost_gen = w.cand_gen;
-  }
-  if (sq) {  // a sequence round: the ledger after K2 (after the join of a split launch), then the walk
-    sr::SeqRound r{};
-    r.d_min = d.d_min;
-    r.cand_global = d.cand_global;
-    r.cand_off = d.cand_off;
-    r.out_status = d.out_status;
-    r.out_node = d.out_node;
-    r.in_off = static_cast<const int32_t*>(ctx->seq_off.p);
-    r.n_cand = d.n_cand;
-    r.floor = sq->floor;
-    r.fb_stop = first_fallback_above(w, sq->floor);
-    r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
-    r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
-    HIP_TRY(ctx, sr::launch_sequence(r, s));
-    return finish_sequence(ctx, sq);
-  }
-  if (early) return finish_early(ctx, out);
-  if (!shm) {  // the shared-memory transport has no collective and no K3 (shm_reduce below)
-    PAIR(2, e2a, e2b);
-    if (collective) {
-      PAIR(3, eca, ecb);
-      if (eca) HIP_TRY(ctx, hipEventRecord(eca, s));
-      sr_status cst = allreduce_min_dev(ctx, d.d_min, 3);  // first ok, first fallback, rank_next
-      if (cst != SR_OK) return cst;
-      if (ecb) HIP_TRY(ctx, hipEventRecord(ecb, s));
-    }
-    HIP_TRY(ctx, sr::launch_winner(d, s, e2a, e2b));
-  }
-#undef PAIR
-  if (timing) ctx->t.n_runs += 1;
-  const int32_t na = d.n_pods, ncand = d.n_cand;
-  if (full || ctx->prof_file) {
-    if (full) {
-      HIP_TRY(ctx, host_reserve(ctx->h_status, sizeof(int32_t) * std::max(1, ncand)));
-      HIP_TRY(ctx, host_reserve(ctx->h_node, sizeof(int32_t) * std::max(1, na)));
-      HIP_TRY(ctx, host_reserve(ctx->h_bytes, sizeof(uint32_t) * std::max(1, ncand)));
-      if (ncand) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status.p, d.out_status, sizeof(int32_t) * ncand, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bytes.p, d.out_bytes, sizeof(uint32_t) * ncand, hipMemcpyDeviceToHost, s));
-      }
-      if (na) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_node.p, d.out_node, sizeof(int32_t) * na, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->in_flight = false;  // (an earlier winner-only run's K2 has finished too)
-  } else if (shm) {
-    // (the walk below waits for the outcome words it needs)
-  } else {
-    // Every result word carries this run's sequence number in its upper
-    // half (K3 stores them without ordering): poll the header, then the
-    // winner's mapping, instead of waking up on stream completion.  A run
-    // that has not finished after 100 ms falls back to the stream (which
-    // also surfaces a kernel fault as an error).
-    const uint32_t tag = static_cast<uint32_t>(d.seq);
-    auto ready = [&](size_t i) { return static_cast<uint32_t>(res[i] >> 32) == tag; };
-    auto header_ready = [&] { return ready(0) && ready(1) && ready(2) && ready(3) && ready(4); };
-    auto map_ready = [&] {
-      if (!static_cast<uint32_t>(res[1])) return true;
-      const size_t np = static_cast<uint32_t>(res[2]);
-      for (size_t q = 0; q < np; ++q)
-        if (!ready(sr::kResultHeader + q)) return false;
-      return true;
-    };
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t spins = 0;
-    while (!(header_ready() && map_ready())) {
-      if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        break;
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-  }
-  if (shm) {  // every rank's outcome words in global order (ms_collective: this host walk)
-    const auto t0 = std::chrono::steady_clock::now();
-    // a winner-only walk returns at the winner: this rank's K2 may still plan
-    // the candidates after it (res_map in h_early, out_status, out_bytes,
-    // out_cycles), as after finish_early; the next prepare settles before it
-    // moves a buffer.  Not after a wait that synchronised the stream (shm_wait)
-    const bool waited = full || ctx->prof_file;  // synchronised above
-    ctx->shm.synced = false;
-    if (!waited) ctx->in_flight = true;  // (also when the walk fails: another rank's words missing)
-    sr_status sst = shm_reduce(ctx, shm_par);
-    if (sst != SR_OK) return sst;
-    if (!waited) ctx->in_flight = !ctx->shm.synced;
-    if (timing & 4) ctx->t.ms_collective += std::chrono::duration<double, std::milli>(
-                                               std::chrono::steady_clock::now() - t0).count();
-  }
+  sr::DevWorkload dp = d, dn = d;
+  dp.list = d.list + n_node;
+  dp.n_list = d.n_list - n_node;
+  dp.n_list_head = 0;
+  dp.n_coop = 0;  // (the general kernel)
+  if (d.list_ext) dp.list_ext = d.list_ext + n_node;
+  dn.n_list = n_node;
+  dn.n_list_head = std::min(d.n_list_head, n_node);
+  dn.max_np = w.max_np_node;
+  dn.dyn_cand = nullptr;  // none of its candidates is on the domain path
+  if (e1a) HIP_TRY(ctx, hipEventRecord(e1a, s));
+  if (!forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+  // the join is the general kernel's own completion signal
+  HIP_TRY(ctx, sr::launch_placement(dp, ctx->stream2, nullptr, ctx->k2_dispatch_events ? ctx->ev_join : nullptr));
+  if (!ctx->k2_dispatch_events) HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+  HIP_TRY(ctx, sr::launch_placement(dn, s, nullptr, nullptr));
+  HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+  if (e1b) HIP_TRY(ctx, hipEventRecord(e1b, s));
+  return SR_OK;
+}
 
-  if (ctx->prof_file && ncand > 0) {  // diagnostics only (tools/k2_profile.py)
-    std::vector<uint64_t> pr(static_cast<size_t>(ncand) * 16 + 2 * sr::kK0ProfWaves);
-    HIP_TRY(ctx, hipMemcpy(pr.data(), d.prof, pr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    const int64_t hdr[2] = {ncand, static_cast<int64_t>(sr::kK0ProfWaves)};
-    std::fwrite(hdr, sizeof(hdr), 1, ctx->prof_file);
-    std::fwrite(pr.data(), sizeof(uint64_t), pr.size(), ctx->prof_file);
-    std::fflush(ctx->prof_file);
+// A sequence round's ledger kernel after K2 (after the join of a split launch).
+sr_status queue_sequence(sr_ctx* ctx, const sr::Workload& w, const SeqWalk& sq) {
+  const sr::DevWorkload& d = ctx->dw;
+  sr::SeqRound r{};
+  r.d_min = d.d_min;
+  r.cand_global = d.cand_global;
+  r.cand_off = d.cand_off;
+  r.out_status = d.out_status;
+  r.out_node = d.out_node;
+  r.in_off = static_cast<const int32_t*>(ctx->seq_off.p);
+  r.n_cand = d.n_cand;
+  r.floor = sq.floor;
+  r.fb_stop = first_fallback_above(w, sq.floor);
+  r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
+  r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
+  HIP_TRY(ctx, sr::launch_sequence(r, ctx->stream));
+  return SR_OK;
+}
+
+// The collective (first ok, first fallback, rank_next) and K3.
+sr_status queue_winner(sr_ctx* ctx, bool collective) {
+  hipStream_t s = ctx->stream;
+  hipEvent_t e2a, e2b, eca, ecb;
+  SR_TRY(event_pair(ctx, 2, &e2a, &e2b));
+  if (collective) {
+    SR_TRY(event_pair(ctx, 3, &eca, &ecb));
+    if (eca) HIP_TRY(ctx, hipEventRecord(eca, s));
+    SR_TRY(allreduce_min_dev(ctx, ctx->dw.d_min, 3));
+    if (ecb) HIP_TRY(ctx, hipEventRecord(ecb, s));
   }
+  HIP_TRY(ctx, sr::launch_winner(ctx->dw, s, e2a, e2b));
+  return SR_OK;
+}
+
+// A full run (or a profiled one): the per-candidate outcomes come down and the
+// stream is waited for.
+sr_status copy_back(sr_ctx* ctx, bool full) {
+  const sr::DevWorkload& d = ctx->dw;
+  hipStream_t s = ctx->stream;
+  const int32_t na = d.n_pods, ncand = d.n_cand;
+  if (full) {
+    HIP_TRY(ctx, host_reserve(ctx->h_status, sizeof(int32_t) * std::max(1, ncand)));
+    HIP_TRY(ctx, host_reserve(ctx->h_node, sizeof(int32_t) * std::max(1, na)));
+    HIP_TRY(ctx, host_reserve(ctx->h_bytes, sizeof(uint32_t) * std::max(1, ncand)));
+    if (ncand) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status.p, d.out_status, sizeof(int32_t) * ncand, hipMemcpyDeviceToHost, s));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bytes.p, d.out_bytes, sizeof(uint32_t) * ncand, hipMemcpyDeviceToHost, s));
+    }
+    if (na) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_node.p, d.out_node, sizeof(int32_t) * na, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  ctx->in_flight = false;  // (an earlier winner-only run's K2 has finished too)
+  return SR_OK;
+}
+
+// Every result word carries this run's sequence number in its upper half (K3
+// stores them without ordering): poll the header, then the winner's mapping,
+// instead of waking up on stream completion.  A run that has not finished
+// after 100 ms falls back to the stream (which also surfaces a kernel fault as
+// an error).
+sr_status poll_result(sr_ctx* ctx) {
+  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
+  const uint32_t tag = static_cast<uint32_t>(ctx->dw.seq);
+  auto ready = [&](size_t i) { return static_cast<uint32_t>(res[i] >> 32) == tag; };
+  auto header_ready = [&] { return ready(0) && ready(1) && ready(2) && ready(3) && ready(4); };
+  auto map_ready = [&] {
+    if (!static_cast<uint32_t>(res[1])) return true;
+    const size_t np = static_cast<uint32_t>(res[2]);
+    for (size_t q = 0; q < np; ++q)
+      if (!ready(sr::kResultHeader + q)) return false;
+    return true;
+  };
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t spins = 0;
+  while (!(header_ready() && map_ready())) {
+    if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      break;
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return SR_OK;
+}
+
+// The shared-memory transport: every rank's outcome words in global order
+// (ms_collective: this host walk).  A winner-only walk returns at the winner:
+// this rank's K2 may still plan the candidates after it (res_map in h_early,
+// out_status, out_bytes, out_cycles), as after finish_early; the next prepare
+// settles before it moves a buffer.  Not after a wait that synchronised the
+// stream (copy_back: `waited`, or shm_wait).
+sr_status walk_shm(sr_ctx* ctx, int shm_par, bool waited) {
+  const auto t0 = std::chrono::steady_clock::now();
+  ctx->shm.synced = false;
+  if (!waited) ctx->in_flight = true;  // (also when the walk fails: another rank's words missing)
+  SR_TRY(shm_reduce(ctx, shm_par));
+  if (!waited) ctx->in_flight = !ctx->shm.synced;
+  if (ctx->timing_cur & 4)
+    ctx->t.ms_collective += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return SR_OK;
+}
+
+// The run's result words (K3's, or the shared-memory walk's) into `out`; a
+// full run adds the per-candidate outcomes copy_back brought down.
+sr_status read_result(sr_ctx* ctx, sr_plan_out* out, bool full) {
+  const sr::Workload& w = ctx->cur->wl;
+  const sr::DevWorkload& d = ctx->dw;
+  const int32_t na = d.n_pods, ncand = d.n_cand;
+  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
   auto val = [&](size_t i) { return static_cast<int32_t>(static_cast<uint32_t>(res[i])); };
   const uint32_t tag = static_cast<uint32_t>(d.seq);
   for (size_t i = 0; i < 5; ++i)
@@ -1465,6 +1167,91 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* 
   out->checks = ctx->issued_known ? ctx->issued_checks : 0;
   return SR_OK;
 }
+
+sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* sq = nullptr) {
+  if (!ctx->prepared) {
+    ctx->err = "sr_plan_run before sr_plan_prepare";
+    return SR_ERR_STATE;
+  }
+  Slot& sl = *ctx->cur;
+  const sr::Workload& w = sl.wl;
+  sr::DevWorkload& d = ctx->dw;
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool collective = has_comm(ctx) && use_comm;
+  // Single rank, winner only: K2 writes each candidate's outcome to the host
+  // and the run returns once the candidates up to the winner are known (no K3)
+  const bool early = !collective && !full && (!ctx->prof_file || sq);
+  ctx->timing_cur = (ctx->timing_runs++ % ctx->timing_every) == 0 ? ctx->timing : 0;
+  do ctx->seq = g_run_seq.fetch_add(1, std::memory_order_relaxed) + 1;
+  while (ctx->seq == 0);  // tag 0 is never used: fresh result memory holds zeros
+  d.seq = ctx->seq;
+  hipEvent_t e0a = nullptr, e0b = nullptr;  // K0's pair only when it is launched (an unrecorded event fails)
+  if (!d.k0_skip) SR_TRY(event_pair(ctx, 0, &e0a, &e0b));
+  // the first run of a candidate generation records its K2 durations (list_cost)
+  const bool want_cost = ctx->list_cost && d.n_list > ctx->list_cost_min && sl.res.want_cost(w);
+  d.out_cycles = nullptr;
+  if (want_cost) {
+    HIP_TRY(ctx, dev_reserve(ctx->out_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand)));
+    HIP_TRY(ctx, host_reserve(sl.h_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand)));
+    if (!sl.ev_cost) HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ev_cost, hipEventDisableTiming));
+    d.out_cycles = static_cast<uint32_t*>(ctx->out_cycles.p);
+  }
+  // d_min alternates between two buffers: K0 resets this run's, K2 the next's
+  const int par = static_cast<int>(ctx->run_count++ & 1);
+  d.d_min = static_cast<int32_t*>(ctx->dmin.p) + 8 * par;
+  d.d_min_next = static_cast<int32_t*>(ctx->dmin.p) + 8 * (1 - par);
+  // the split launch: the encoder put the node-order candidates first
+  const bool split = ctx->k2_split && w.n_list_node > 0 && w.n_list_node < d.n_list &&
+                     sr::k2_node_launch(false, d.k2_mode, w.max_np_node, d.k2_node_kernel);
+  if (split && !ctx->stream2) {
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+  }
+  bool forked = false;
+  SR_TRY(queue_tables(ctx, sl, split, par, e0a, e0b, &forked));
+  hipEvent_t e1a, e1b;
+  SR_TRY(event_pair(ctx, 1, &e1a, &e1b));
+  const bool shm = collective && ctx->shm.host;  // ranks reduce through host memory: no collective, no K3
+  int shm_par = 0;
+  if (early) {
+    d.res_stat = ctx->d_early;
+    d.res_map = ctx->d_early + d.n_cand;
+  } else if (shm) {
+    SR_TRY(shm_publish(ctx, &shm_par));
+  } else {
+    d.res_stat = d.res_map = nullptr;
+  }
+  SR_TRY(queue_placement(ctx, sl, split, forked, e1a, e1b));
+  if (want_cost) {  // after K2 in stream order: the next prepare waits for it (ev_cost)
+    HIP_TRY(ctx, hipMemcpyAsync(sl.h_cycles.p, d.out_cycles, sizeof(uint32_t) * static_cast<size_t>(d.n_cand),
+                                hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipEventRecord(sl.ev_cost, s));
+    sl.res.cost_queued(w);
+  }
+  if (sq) {  // a sequence round: the ledger after K2, then the walk
+    SR_TRY(queue_sequence(ctx, w, *sq));
+    return finish_sequence(ctx, sq);
+  }
+  if (early) return finish_early(ctx, out);
+  if (!shm) SR_TRY(queue_winner(ctx, collective));  // the shared-memory transport has neither (walk_shm below)
+  if (ctx->timing_cur) ctx->t.n_runs += 1;
+  const bool waited = full || ctx->prof_file;
+  if (waited) SR_TRY(copy_back(ctx, full));
+  else if (!shm) SR_TRY(poll_result(ctx));
+  if (shm) SR_TRY(walk_shm(ctx, shm_par, waited));  // (waits for the outcome words it needs)
+  if (ctx->prof_file && d.n_cand > 0) {  // diagnostics only (tools/k2_profile.py)
+    std::vector<uint64_t> pr(static_cast<size_t>(d.n_cand) * 16 + 2 * sr::kK0ProfWaves);
+    HIP_TRY(ctx, hipMemcpy(pr.data(), d.prof, pr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const int64_t hdr[2] = {d.n_cand, static_cast<int64_t>(sr::kK0ProfWaves)};
+    std::fwrite(hdr, sizeof(hdr), 1, ctx->prof_file);
+    std::fwrite(pr.data(), sizeof(uint64_t), pr.size(), ctx->prof_file);
+    std::fflush(ctx->prof_file);
+  }
+  return read_result(ctx, out, full);
+}
+#undef SR_TRY
 
 }  // namespace
 
