@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SR_ABI_VERSION 10
+#define SR_ABI_VERSION 11
 
 /* ------------------------------------------------------------------ status */
 typedef int32_t sr_status;
@@ -96,6 +96,7 @@ typedef int32_t sr_status;
 #define SR_CAND_SKIPPED   (-4)  /* sr_plan_first: after the first drainable candidate, never evaluated
                                    (run() drains it and breaks, rescheduler.go:280-286); sr_plan_sequence:
                                    below first_cand, or after the pass stopped */
+#define SR_CAND_PDB       (-5)  /* sr_plan_sequence_pdb: draining it would exceed a group's allowance; not planned */
 
 /* ------------------------------------------------------------- cluster model */
 /* Nodes (k8s.io/api/core/v1 Node), in the order the node lister returned them
@@ -512,7 +513,7 @@ const char *sr_build_info(void);
  * added sr_cluster.volumes and pod_stamp; ABI 6 the sr_timing enc_reused /
  * enc_pod_patches counters, which sr_get_timing writes; ABI 7 sr_timing.ms_collective; ABI 8
  * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields; ABI 10
- * sr_plan_sequence). */
+ * sr_plan_sequence; ABI 11 sr_plan_sequence_pdb). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -625,6 +626,38 @@ typedef struct {
 } sr_sequence_out;
 sr_status sr_plan_sequence(sr_ctx *ctx, sr_snapshot *snap /* modified */, const sr_cluster *cluster,
                            const sr_candidates *cands, sr_sequence_out *out);
+
+/* sr_plan_sequence under PodDisruptionBudgets (ABI 11).  The reference evicts
+ * one node's pods per tick, so the eviction API's budget check is never asked
+ * for much at once; a sequence evicts many replicas of one Deployment in one
+ * tick.  The shim already holds allPDBs (rescheduler.go:231): it passes one
+ * disruption group per PDB with a pod in the list, `allowed` from the PDB
+ * status' allowed disruptions, and the group of each candidate pod.  A pod
+ * belongs to at most one group: a pod several PDBs select gets a group of its
+ * own with allowed = 0 (the v1.19 eviction API refuses such pods).  The pass is
+ * sr_plan_sequence's with one check, made before anything else is asked of a
+ * candidate with pods:
+ *
+ *     need[g] = pods of c in group g
+ *     some need[g] > remaining[g]: status[c] = SR_CAND_PDB, continue
+ *
+ * and, when c drains, remaining[g] -= need[g].  A refused candidate is never
+ * planned (node_of_pod -1, the snapshot untouched) and does not stop the pass
+ * even when it lies outside the encoded predicate set; allowances only fall
+ * during a pass, so it stays refused.  limits == NULL or n_groups == 0 is
+ * sr_plan_sequence itself.  To resume after SR_SEQ_FALLBACK the shim calls
+ * again with allowed = remaining (less stop_cand's pods when it drained that
+ * candidate on the Go path).  SR_ERR_INVALID_ARG also for n_groups < 0, a NULL
+ * allowed or pod_group with n_groups > 0, a negative allowance, and a group id
+ * outside [-1, n_groups); nothing is committed on an argument error. */
+typedef struct {
+  int32_t        n_groups;   /* disruption groups (PDBs); 0 = no limits */
+  const int32_t *allowed;    /* [n_groups] evictions still allowed per group (the PDB status' allowed disruptions), >= 0 */
+  const int32_t *pod_group;  /* [cand_pod_off[n_cand] - cand_pod_off[0]] parallel to cand_pods: group of each pod, -1 none */
+  int32_t       *remaining;  /* [n_groups] optional out: allowed minus the drained candidates' pods */
+} sr_pdb_limits;
+sr_status sr_plan_sequence_pdb(sr_ctx *ctx, sr_snapshot *snap /* modified */, const sr_cluster *cluster,
+                               const sr_candidates *cands, const sr_pdb_limits *limits, sr_sequence_out *out);
 
 /* Split form of sr_plan for a resident workload (bench): prepare = host
  * encoding + upload; run = device-only tick over the resident buffers

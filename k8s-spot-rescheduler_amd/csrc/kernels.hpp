@@ -162,4 +162,27 @@ struct SeqRound {
 // into the ledger (after K2 in stream order; no host synchronisation).
 hipError_t launch_sequence(const SeqRound& r, hipStream_t s);
 
+// One round of sr_plan_sequence_pdb (seq_pdb.hip): the ledger
+// step that knows the disruption budgets.  The round's winner is not d_min[0]
+// but the first candidate in (floor, fb_stop) that K2 found drainable and whose
+// needs the device-resident allowances cover; fb_stop is the first UNREFUSED
+// fallback candidate above the floor.
+constexpr int kPdbHeader = 2;  // words before the winner's mapping in `words`
+struct SeqPdbRound {
+  SeqRound r;                 // (d_min is not read)
+  const int32_t* need_off;    // [candidates of the caller's list + 1] the candidates' needs, a CSR of
+  const int32_t* need_group;  //   (group, count) by the caller's candidate index, a group once per candidate
+  const int32_t* need_count;
+  int32_t* remaining;         // [n_groups] evictions still allowed; the winner's needs are subtracted here
+  uint8_t* refused;           // [n_cand] out: the round's refused flags of the active candidates
+  int32_t* win;               // [2] out: {the winner's index in the caller's list (INT32_MAX: none), its active index}
+  uint64_t* words;            // mapped host memory [kPdbHeader + max pods] words seq << 32 | value:
+                              //   {winner (-1: none), npods, mapping...}
+  uint32_t seq;               // the round's run sequence number
+};
+// Two launches in stream order after K2 (after the join of a split launch), no
+// host synchronisation: one block finds the winner, publishes it and commits
+// its needs; a grid then copies the judged candidates into the ledger.
+hipError_t launch_sequence_pdb(const SeqPdbRound& p, hipStream_t s);
+
 }  // namespace sr

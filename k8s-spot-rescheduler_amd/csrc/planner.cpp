@@ -23,6 +23,7 @@
 #include "host.hpp"
 #include "kernels.hpp"
 #include "residency.hpp"
+#include "seq_pdb.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -141,6 +142,10 @@ struct sr_ctx {
   // at the end of the sequence) and the caller's cand_pod_off on the device
   DevBuf seq_status, seq_node, seq_off;
   HostBuf h_seq_status, h_seq_node, h_seq_off;
+  // sr_plan_sequence_pdb: the candidates' needs {off, group, count} and the allowances, uploaded once per call
+  // from h_pdb; the round's refused flags and {winner, active index} (seq_pdb.hip)
+  DevBuf pdb_need, pdb_remaining, pdb_refused, pdb_win;
+  HostBuf h_pdb;
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   uint64_t run_count = 0;      // runs of this context: d_min alternates between two buffers
@@ -844,6 +849,10 @@ struct SeqWalk {
   int32_t fallback = -1;  // out: the fallback candidate the walk stopped at
   int32_t end = -1;       // out: the last candidate the walk judged (below the fallback it stopped at)
   std::vector<int32_t> map;  // out: the winner's mapping
+  // sr_plan_sequence_pdb: the needs and the host's mirror of the device's allowances (null: no limits), and the
+  // round's first unrefused fallback candidate above the floor (INT32_MAX: none)
+  sr::PdbLedger* pdb = nullptr;
+  int32_t stop = INT32_MAX;
 };
 
 // The first fallback candidate above the floor (INT32_MAX: none).
@@ -912,6 +921,64 @@ sr_status finish_sequence(sr_ctx* ctx, SeqWalk* sq) {
     std::atomic_thread_fence(std::memory_order_acquire);
     sq->map.resize(static_cast<size_t>(np));
     for (int32_t q = 0; q < np; ++q) sq->map[q] = static_cast<int32_t>(static_cast<uint32_t>(map[o + q]));
+  }
+  if (synced) ctx->in_flight = false;
+  return SR_OK;
+}
+
+// The end of a round under disruption budgets: the round's winner is the
+// ledger step's (seq_pdb.hip), not the first drainable candidate of K2's words
+// -- that one may be refused, and K2 wrote no other candidate's mapping to the
+// host.  The step runs after the whole of K2, so its words are waited for
+// instead of K2's.
+sr_status finish_sequence_pdb(sr_ctx* ctx, SeqWalk* sq) {
+  const sr::Workload& w = ctx->cur->wl;
+  const sr::DevWorkload& d = ctx->dw;
+  if (ctx->timing_cur) ctx->t.n_runs += 1;
+  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
+  const uint32_t tag = d.seq;
+  auto ready = [&](size_t i) { return static_cast<uint32_t>(res[i] >> 32) == tag; };
+  auto val = [&](size_t i) { return static_cast<int32_t>(static_cast<uint32_t>(res[i])); };
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t spins = 0;
+  bool synced = false;
+  auto wait = [&](size_t i) -> sr_status {
+    while (!ready(i)) {
+      if (!synced && (++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        synced = true;
+      }
+      if (synced && !ready(i)) {
+        ctx->err = "ledger result word not written by this round";
+        return SR_ERR_HIP;
+      }
+    }
+    return SR_OK;
+  };
+  ctx->in_flight = true;  // the ledger copy may still run (also when the wait fails)
+  sq->winner = sq->fallback = -1;
+  sq->end = w.n_input_cand - 1;
+  for (size_t i = 0; i < static_cast<size_t>(sr::kPdbHeader); ++i) {
+    sr_status st = wait(i);
+    if (st != SR_OK) return st;
+  }
+  const int32_t win = val(0), np = val(1);
+  if (win >= 0) {
+    if (win <= sq->floor || win >= w.n_input_cand || np < 0 || np > w.max_cand_pods) {
+      ctx->err = "ledger result names no candidate of this round";
+      return SR_ERR_HIP;
+    }
+    for (int32_t q = 0; q < np; ++q) {
+      sr_status st = wait(static_cast<size_t>(sr::kPdbHeader + q));
+      if (st != SR_OK) return st;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    sq->map.resize(static_cast<size_t>(np));
+    for (int32_t q = 0; q < np; ++q) sq->map[q] = val(static_cast<size_t>(sr::kPdbHeader + q));
+    sq->winner = sq->end = win;
+  } else if (sq->stop != INT32_MAX) {
+    sq->fallback = sq->stop;
+    sq->end = sq->stop - 1;
   }
   if (synced) ctx->in_flight = false;
   return SR_OK;
@@ -1029,6 +1096,35 @@ sr_status queue_sequence(sr_ctx* ctx, const sr::Workload& w, const SeqWalk& sq) 
   r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
   r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
   HIP_TRY(ctx, sr::launch_sequence(r, ctx->stream));
+  return SR_OK;
+}
+
+// ... under disruption budgets: the step that finds the round's winner itself.
+sr_status queue_sequence_pdb(sr_ctx* ctx, const SeqWalk& sq) {
+  const sr::DevWorkload& d = ctx->dw;
+  const int32_t* need = static_cast<const int32_t*>(ctx->pdb_need.p);
+  const size_t n = sq.pdb->need_off.size() - 1, nn = sq.pdb->need_group.size();
+  sr::SeqPdbRound p{};
+  p.r.d_min = d.d_min;
+  p.r.cand_global = d.cand_global;
+  p.r.cand_off = d.cand_off;
+  p.r.out_status = d.out_status;
+  p.r.out_node = d.out_node;
+  p.r.in_off = static_cast<const int32_t*>(ctx->seq_off.p);
+  p.r.n_cand = d.n_cand;
+  p.r.floor = sq.floor;
+  p.r.fb_stop = sq.stop;
+  p.r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
+  p.r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
+  p.need_off = need;
+  p.need_group = need + n + 1;
+  p.need_count = need + n + 1 + nn;
+  p.remaining = static_cast<int32_t*>(ctx->pdb_remaining.p);
+  p.refused = static_cast<uint8_t*>(ctx->pdb_refused.p);
+  p.win = static_cast<int32_t*>(ctx->pdb_win.p);
+  p.words = d.result;  // (sized by prepare for the longest candidate; a sequence round launches no K3)
+  p.seq = d.seq;
+  HIP_TRY(ctx, sr::launch_sequence_pdb(p, ctx->stream));
   return SR_OK;
 }
 
@@ -1231,6 +1327,10 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* 
     sl.res.cost_queued(w);
   }
   if (sq) {  // a sequence round: the ledger after K2, then the walk
+    if (sq->pdb) {
+      SR_TRY(queue_sequence_pdb(ctx, *sq));
+      return finish_sequence_pdb(ctx, sq);
+    }
     SR_TRY(queue_sequence(ctx, w, *sq));
     return finish_sequence(ctx, sq);
   }
@@ -1315,7 +1415,8 @@ void sr_destroy(sr_ctx* ctx) {
     if (ctx->rank == 0) shm_unlink(ctx->shm.name.c_str());  // the ranks keep their mappings
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
-                    &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off})
+                    &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off, &ctx->pdb_need, &ctx->pdb_remaining,
+                    &ctx->pdb_refused, &ctx->pdb_win})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1324,7 +1425,7 @@ void sr_destroy(sr_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->out_cycles.p) (void)hipFree(ctx->out_cycles.p);
   for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm,
-                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off})
+                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb})
     if (b->p) (void)hipHostFree(b->p);
   for (auto& sl : ctx->slots) {
     if (sl->arena.p) (void)hipFree(sl->arena.p);
@@ -1459,8 +1560,12 @@ static sr_status plan_first(sr_ctx* ctx, const sr_snapshot* snap, const sr_clust
 // the cursor from the current snapshot (K2 skips the others: cand_floor); its
 // first drainable candidate is the next drain, the candidates between the
 // cursor and it failed against the state the serial pass would have shown them.
-sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                           sr_sequence_out* out) {
+// With limits (sr_plan_sequence_pdb) a round's refused set is
+// fixed by the allowances the last commit left: the host's mirror decides
+// which fallback candidate stops the round and whether a round is needed, the
+// device's ledger step finds the winner among the unrefused candidates.
+static sr_status plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                               const sr_pdb_limits* limits, sr_sequence_out* out) {
   if (!ctx || !snap || !cluster || !cands || !out || cands->n_cand < 0) return SR_ERR_INVALID_ARG;
   const int32_t n = cands->n_cand;
   out->n_drained = out->rounds = out->rounds_k0 = out->rounds_reused = 0;
@@ -1484,12 +1589,31 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
   }
   const int32_t* off = cands->cand_pod_off;
   const int32_t n_pods = n > 0 ? off[n] - off[0] : 0;
+  sr::PdbLedger pdb;
+  const bool limited = limits && limits->n_groups != 0;
+  if (limited) {
+    if (const char* why = sr::pdb_validate(limits->n_groups, limits->allowed, limits->pod_group, n_pods)) {
+      ctx->err = why;
+      return SR_ERR_INVALID_ARG;
+    }
+    sr::pdb_build(n, off, limits->n_groups, limits->allowed, limits->pod_group, &pdb);
+  }
+  // limits->remaining follows the commits, also when a later round fails
+  struct Remaining {
+    const sr::PdbLedger& l;
+    int32_t* out;
+    ~Remaining() {
+      if (out) std::copy(l.remaining.begin(), l.remaining.end(), out);
+    }
+  } remaining_out{pdb, limited ? limits->remaining : nullptr};
   const bool want = out->status != nullptr || out->node_of_pod != nullptr;
-  // what the host knows of each candidate: 0 not judged, 1 judged on the device (the ledger), 2 no pods, 3 fallback
+  // what the host knows of each candidate: 0 not judged, 1 judged on the device (the ledger), 2 no pods, 3 fallback,
+  // 4 refused (decided by the host: a fallback candidate, or no round ran)
   std::vector<uint8_t> how(static_cast<size_t>(n), 0);
   int32_t cursor = out->first_cand - 1;
   bool ledger = false;  // the device arrays are sized and cand_pod_off is up
   SeqWalk sq;
+  if (limited) sq.pdb = &pdb;
   for (;;) {
     // candidates without pods need no round (rescheduler.go:260-264); no round when nothing else is left
     int32_t next = cursor + 1;
@@ -1499,7 +1623,15 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
     if (st != SR_OK) return st;
     const sr::Workload& w = ctx->cur->wl;
     sq.floor = cursor;
-    const bool any_active = !w.cand_src.empty() && w.cand_src.back() > cursor;
+    bool any_active = !w.cand_src.empty() && w.cand_src.back() > cursor;
+    if (limited) {  // no round when every candidate with pods below the stop is refused or host-decided
+      sq.stop = sr::pdb_first_stop(pdb, cursor, n, [&](int32_t i) { return w.status_host[i] == SR_CAND_FALLBACK; });
+      any_active = false;
+      for (auto k = std::upper_bound(w.cand_src.begin(), w.cand_src.end(), cursor);
+           k != w.cand_src.end() && *k < sq.stop && !any_active; ++k)
+        any_active = !pdb.refused(*k);
+    }
+    const bool in_round = any_active;
     if (any_active) {
       if (!ledger) {  // (after prepare's settle: no earlier kernel reads them)
         HIP_TRY(ctx, dev_reserve(ctx->seq_status, sizeof(int32_t) * static_cast<size_t>(n)));
@@ -1509,6 +1641,24 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
         std::memcpy(ctx->h_seq_off.p, off, sizeof(int32_t) * (static_cast<size_t>(n) + 1));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_off.p, ctx->h_seq_off.p, sizeof(int32_t) * (static_cast<size_t>(n) + 1),
                                     hipMemcpyHostToDevice, ctx->stream));
+        if (limited) {  // the needs and the allowances go up once per call; the device commits by itself
+          const size_t nn = pdb.need_group.size(), ng = pdb.remaining.size();
+          const size_t need_words = static_cast<size_t>(n) + 1 + 2 * nn;
+          HIP_TRY(ctx, dev_reserve(ctx->pdb_need, sizeof(int32_t) * need_words));
+          HIP_TRY(ctx, dev_reserve(ctx->pdb_remaining, sizeof(int32_t) * ng));
+          HIP_TRY(ctx, dev_reserve(ctx->pdb_refused, static_cast<size_t>(n)));
+          HIP_TRY(ctx, dev_reserve(ctx->pdb_win, 2 * sizeof(int32_t)));
+          HIP_TRY(ctx, host_reserve(ctx->h_pdb, sizeof(int32_t) * (need_words + ng)));
+          int32_t* up = static_cast<int32_t*>(ctx->h_pdb.p);
+          std::copy(pdb.need_off.begin(), pdb.need_off.end(), up);
+          std::copy(pdb.need_group.begin(), pdb.need_group.end(), up + n + 1);
+          std::copy(pdb.need_count.begin(), pdb.need_count.end(), up + n + 1 + nn);
+          std::copy(pdb.remaining.begin(), pdb.remaining.end(), up + need_words);
+          HIP_TRY(ctx, hipMemcpyAsync(ctx->pdb_need.p, up, sizeof(int32_t) * need_words, hipMemcpyHostToDevice,
+                                      ctx->stream));
+          HIP_TRY(ctx, hipMemcpyAsync(ctx->pdb_remaining.p, up + need_words, sizeof(int32_t) * ng,
+                                      hipMemcpyHostToDevice, ctx->stream));
+        }
         ledger = true;
       }
       ctx->dw.cand_floor = cursor;
@@ -1523,10 +1673,16 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
     } else {  // every candidate above the cursor is decided by the host
       sq.winner = sq.fallback = -1;
       sq.end = n - 1;
-      const int32_t fb = first_fallback_above(w, cursor);
+      const int32_t fb = limited ? sq.stop : first_fallback_above(w, cursor);
       if (fb != INT32_MAX) sq.fallback = fb, sq.end = fb - 1;
     }
-    for (int32_t i = cursor + 1; i <= sq.end; ++i) how[i] = w.status_host[i] == SR_CAND_EMPTY ? 2 : 1;
+    for (int32_t i = cursor + 1; i <= sq.end; ++i) {
+      how[i] = w.status_host[i] == SR_CAND_EMPTY ? 2 : 1;
+      // a refused candidate the round's K2 planned is in the ledger as refused (the allowances are still the round's)
+      if (limited && how[i] == 1 && pdb.refused(i) &&
+          !(in_round && std::binary_search(w.cand_src.begin(), w.cand_src.end(), i)))
+        how[i] = 4;
+    }
     if (sq.winner < 0) {
       if (sq.fallback >= 0) {
         how[sq.fallback] = 3;
@@ -1549,6 +1705,7 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
     }
     for (int32_t q = 0; q < np; ++q) sr::snapshot_add_pod(snap, cluster, cands->cand_pods[off[c] + q], sq.map[q]);
     out->drained[out->n_drained++] = c;
+    if (limited) pdb.commit(c);
     cursor = c;
     if (out->n_drained == out->max_drains) {
       out->stop = SR_SEQ_BUDGET;
@@ -1574,12 +1731,23 @@ sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
     for (int32_t i = 0; i < n; ++i) {
       const bool dev = how[i] == 1;
       if (out->status)
-        out->status[i] = dev ? hs[i] : how[i] == 2 ? SR_CAND_EMPTY : how[i] == 3 ? SR_CAND_FALLBACK : SR_CAND_SKIPPED;
+        out->status[i] = dev ? hs[i] : how[i] == 2 ? SR_CAND_EMPTY : how[i] == 3 ? SR_CAND_FALLBACK
+                                   : how[i] == 4 ? SR_CAND_PDB : SR_CAND_SKIPPED;
       if (out->node_of_pod)
         for (int32_t q = off[i] - off[0]; q < off[i + 1] - off[0]; ++q) out->node_of_pod[q] = dev ? hn[q] : -1;
     }
   }
   return SR_OK;
+}
+
+sr_status sr_plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                           sr_sequence_out* out) {
+  return plan_sequence(ctx, snap, cluster, cands, nullptr, out);
+}
+
+sr_status sr_plan_sequence_pdb(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                               const sr_pdb_limits* limits, sr_sequence_out* out) {
+  return plan_sequence(ctx, snap, cluster, cands, limits, out);
 }
 
 // Single-process helpers (no collective): findSpotNodeForPod / canDrainNode.

@@ -169,6 +169,10 @@ class sr_sequence_out(_KeepsArrays):
                 ("drained", P32), ("status", P32), ("node_of_pod", P32)]
 
 
+class sr_pdb_limits(_KeepsArrays):
+    _fields_ = [("n_groups", ctypes.c_int32), ("allowed", P32), ("pod_group", P32), ("remaining", P32)]
+
+
 # sr_allreduce_min_fn: int32 fn(void *user, uint64_t *words, int32_t n)
 ALLREDUCE_MIN_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32)
 
@@ -388,6 +392,9 @@ def _declare_planner(lib):
     lib.sr_plan_first.restype = S
     lib.sr_plan_sequence.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_sequence_out)]
     lib.sr_plan_sequence.restype = S
+    lib.sr_plan_sequence_pdb.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_pdb_limits),
+                                         ctypes.POINTER(sr_sequence_out)]
+    lib.sr_plan_sequence_pdb.restype = S
     lib.sr_plan_prepare.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates)]
     lib.sr_plan_prepare.restype = S
     lib.sr_plan_run.argtypes = [VP, ctypes.POINTER(sr_plan_out)]
@@ -413,6 +420,7 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_destroy",
             "sr_snapshot_add_pod", "sr_snapshot_fork", "sr_snapshot_revert", "sr_snapshot_node_state",
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
-            "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_plan", "sr_plan_first", "sr_plan_sequence", "sr_plan_prepare", "sr_plan_run",
+            "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_plan", "sr_plan_first", "sr_plan_sequence",
+            "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",
             "sr_comm_init_shm"]

@@ -214,15 +214,26 @@ class SequenceResult:
     rounds: int              # device rounds; of which launched K0 / kept the candidate side
     rounds_k0: int
     rounds_reused: int
+    remaining: Optional[np.ndarray] = None  # with limits: evictions each group still allows after the pass
+
+
+@dataclass
+class PdbLimits:
+    """Disruption groups for sr_plan_sequence_pdb: `allowed[g]` evictions group g still allows (the PDB status'
+    allowed disruptions), `pod_group[q]` the group of candidate pod q (parallel to cand_pods; -1: none).  A pod
+    selected by several PDBs gets a group of its own with allowed = 0."""
+    allowed: np.ndarray
+    pod_group: np.ndarray
 
 
 def plan_sequence_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
                          cand_pods: np.ndarray, max_drains: Optional[int] = None, first_cand: int = 0,
-                         full: bool = True) -> SequenceResult:
+                         full: bool = True, limits: Optional[PdbLimits] = None) -> SequenceResult:
     """sr_plan_sequence over caller-built arrays: the loop of rescheduler.go:228-287 with
     the `break` at :286 replaced by "keep the forked state and go on", up to max_drains
     (None: no budget).  The snapshot is modified: afterwards it holds every drained
-    candidate's pods on their planned nodes."""
+    candidate's pods on their planned nodes.  With `limits` the pass is sr_plan_sequence_pdb's: a
+    candidate whose pods would exceed a group's allowance gets SR_CAND_PDB and is not planned."""
     lib = predicateChecker.lib
     n = len(cand_off) - 1
     budget = 2 ** 31 - 1 if max_drains is None else int(max_drains)  # None: no budget (the pass ends with SR_SEQ_END)
@@ -237,24 +248,42 @@ def plan_sequence_arrays(predicateChecker: PredicateChecker, snapshot_handle, cl
     o.drained = capi.ptr(drained, capi.P32)
     o.status = capi.ptr(status, capi.P32) if full else None
     o.node_of_pod = capi.ptr(nodes, capi.P32) if full else None
-    st = lib.sr_plan_sequence(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c), ctypes.byref(o))
+    remaining = None
+    if limits is None:
+        name = "sr_plan_sequence"
+        st = lib.sr_plan_sequence(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                                  ctypes.byref(o))
+    else:
+        name = "sr_plan_sequence_pdb"
+        allowed = np.ascontiguousarray(limits.allowed, np.int32)
+        pod_group = np.ascontiguousarray(limits.pod_group, np.int32)
+        if len(pod_group) != n_pods:
+            raise ValueError("limits.pod_group has %d entries for %d candidate pods" % (len(pod_group), n_pods))
+        remaining = np.full(max(len(allowed), 1), -1, np.int32)
+        lim = capi.sr_pdb_limits(len(allowed), capi.ptr(allowed, capi.P32), capi.ptr(pod_group, capi.P32),
+                                 capi.ptr(remaining, capi.P32))
+        st = lib.sr_plan_sequence_pdb(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                                      ctypes.byref(lim), ctypes.byref(o))
+        remaining = remaining[:len(allowed)]
     if st != capi.SR_OK:
-        err = PlannerError("sr_plan_sequence: %d %s" % (st, predicateChecker.last_error()))
+        err = PlannerError("%s: %d %s" % (name, st, predicateChecker.last_error()))
         err.status = st
         err.drained = drained[: o.n_drained].copy()  # what the snapshot already holds
         raise err
     return SequenceResult(drained[: o.n_drained].copy(), o.stop, o.stop_cand, status[:n], nodes[:n_pods],
-                          o.rounds, o.rounds_k0, o.rounds_reused)
+                          o.rounds, o.rounds_k0, o.rounds_reused, remaining)
 
 
 def drainSequence(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
-                  candidates: Sequence[Sequence[Pod]], max_drains: Optional[int] = None, first_cand: int = 0):
+                  candidates: Sequence[Sequence[Pod]], max_drains: Optional[int] = None, first_cand: int = 0,
+                  limits: Optional[PdbLimits] = None):
     """Several consistent drains in one tick, in the style of canDrainNode: `candidates`
     are the podsForDeletion lists of the on-demand nodes in NodeInfoArray order.  Returns
     (SequenceResult, plans) with plans = [(candidate index, [spot node name per pod])] in
     drain order; the snapshot keeps the drained candidates' pods.  On SR_SEQ_FALLBACK the
     caller judges candidate `stop_cand` with the reference path and calls again with
-    first_cand = stop_cand + 1."""
+    first_cand = stop_cand + 1 (and, with `limits`, allowed = the result's `remaining`, less
+    stop_cand's pods if it drained that candidate; pod_group follows the flattened candidates)."""
     _check_order(spotSnapshot, nodes)
     flat = [p for c in candidates for p in c]
     enc = spotSnapshot.encode_pods(flat)
@@ -262,7 +291,7 @@ def drainSequence(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnaps
     cand_off[1:] = np.cumsum([len(c) for c in candidates])
     cand_pods = np.arange(len(flat), dtype=np.int32)
     r = plan_sequence_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off, cand_pods, max_drains,
-                             first_cand)
+                             first_cand, limits=limits)
     plans = []
     for c in r.drained:
         seg = r.node_of_pod[cand_off[c]:cand_off[c + 1]]
