@@ -25,6 +25,7 @@ enum { kEnd = 0, kBudget = 1, kStopFallback = 2 };
 struct Pass {
   std::vector<int32_t> status, drained, remaining;
   int32_t stop = kEnd, stop_cand = -1, rounds = 0;
+  int32_t by_last_need = 0;  // (naive) refusals of a candidate with several needs that only its last need decides
   bool operator==(const Pass& o) const {
     return status == o.status && drained == o.drained && remaining == o.remaining && stop == o.stop &&
            stop_cand == o.stop_cand;
@@ -48,14 +49,20 @@ Pass naive(const List& in) {
       r.status[c] = kEmpty;
       continue;
     }
-    bool refused = false;
-    for (size_t g = 0; g < in.allowed.size() && !refused; ++g) {
+    // (groups ascending, as the needs of the CSR: the last group with pods is the candidate's last need)
+    int32_t needs = 0, over = 0;
+    bool last_over = false;
+    for (size_t g = 0; g < in.allowed.size(); ++g) {
       int32_t need = 0;
       for (int32_t q = in.off[c] - base; q < in.off[c + 1] - base; ++q) need += in.pod_group[q] == static_cast<int32_t>(g);
-      refused = need > r.remaining[g];
+      if (need == 0) continue;
+      last_over = need > r.remaining[g];
+      needs += 1;
+      over += last_over;
     }
-    if (refused) {
+    if (over > 0) {
       r.status[c] = kPdb;
+      r.by_last_need += needs > 1 && over == 1 && last_over;
       continue;
     }
     if (in.kind[c] == sr::kPdbFallback) {
@@ -120,6 +127,25 @@ Pass rounds(const List& in) {
   return r;
 }
 
+// Three candidates of m pods, pod k in group k; every group allows two evictions, the last one only one.  The
+// first candidate is accepted with its last need exactly at the allowance and commits m needs; the other two
+// meet m - 1 needs that still hold and are refused by the last one alone.
+bool many_needs_case(int m) {
+  List in;
+  in.off = {3, 3 + m, 3 + 2 * m, 3 + 3 * m};
+  in.kind.assign(3, sr::kPdbDrains);
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < m; ++k) in.pod_group.push_back(k);
+  in.allowed.assign(static_cast<size_t>(m), 2);
+  in.allowed.back() = 1;
+  in.max_drains = 1 << 30;
+  const Pass a = naive(in), b = rounds(in);
+  std::vector<int32_t> left(static_cast<size_t>(m), 1);
+  left.back() = 0;
+  return a == b && b.status == std::vector<int32_t>{kOk, kPdb, kPdb} && b.drained == std::vector<int32_t>{0} &&
+         b.remaining == left && b.stop == kEnd && b.rounds == 1 && a.by_last_need == 2;
+}
+
 int fail(const char* what, uint32_t seed, int i) {
   std::fprintf(stderr, "seq_pdb_check: %s (seed %u, list %d)\n", what, seed, i);
   return 1;
@@ -132,7 +158,7 @@ int main(int argc, char** argv) {
   const uint32_t seed = argc > 2 ? static_cast<uint32_t>(std::strtoul(argv[2], nullptr, 10)) : 1u;
   std::mt19937 rng(seed);
   auto pick = [&](int lo, int hi) { return lo + static_cast<int>(rng() % static_cast<uint32_t>(hi - lo + 1)); };
-  long refusals = 0, drains = 0, stops = 0, passed_fallbacks = 0, n_rounds = 0;
+  long refusals = 0, drains = 0, stops = 0, passed_fallbacks = 0, n_rounds = 0, by_last_need = 0;
   for (int i = 0; i < lists; ++i) {
     List in;
     const int n = pick(0, 40), groups = pick(1, 8);
@@ -162,7 +188,10 @@ int main(int argc, char** argv) {
     drains += static_cast<long>(a.drained.size());
     stops += a.stop == kStopFallback;
     n_rounds += b.rounds;
+    by_last_need += a.by_last_need;
   }
+  for (int m : {2, 64, 65, 300, 1025})
+    if (!many_needs_case(m)) return fail("many needs, decided by the last one", seed, -m);
   // the argument rules
   const int32_t allowed[2] = {1, 0}, neg[2] = {1, -1}, group[3] = {0, -1, 1}, high[3] = {0, 2, 1}, low[3] = {0, -2, 1};
   bool ok = !sr::pdb_validate(2, allowed, group, 3) && !sr::pdb_validate(0, nullptr, nullptr, 3) &&
@@ -171,8 +200,10 @@ int main(int argc, char** argv) {
             sr::pdb_validate(2, neg, group, 3) && sr::pdb_validate(2, allowed, high, 3) &&
             sr::pdb_validate(2, allowed, low, 3);
   if (!ok) return fail("the argument rules", seed, -1);
-  if (lists >= 1000 && !(refusals && drains && stops && passed_fallbacks)) return fail("a vacuous run", seed, -1);
-  std::printf("seq_pdb_check ok: %d lists, %ld drains, %ld refusals (%ld of fallback candidates), %ld fallback stops, "
-              "%ld rounds\n", lists, drains, refusals, passed_fallbacks, stops, n_rounds);
+  if (lists >= 1000 && !(refusals && drains && stops && passed_fallbacks && by_last_need))
+    return fail("a vacuous run", seed, -1);
+  std::printf("seq_pdb_check ok: %d lists, %ld drains, %ld refusals (%ld of fallback candidates, %ld decided by the "
+              "last of several needs), %ld fallback stops, %ld rounds\n", lists, drains, refusals, passed_fallbacks,
+              by_last_need, stops, n_rounds);
   return 0;
 }
