@@ -74,13 +74,14 @@ def test_gpu_random_shared_key_plans(checker, seed):
 @pytest.mark.gpu
 def test_gpu_domain_path_up_to_512_pods(checker):
     """Up to 512 pods interacting across nodes are planned on the device
-    (8 groups of 64 lanes: candidates of 300 and 512 pods, and 257 / 256 / 65 /
-    64 around the group boundaries), bit-exact with the oracle; a 513-pod
+    (8 groups of 64 lanes: candidates of 300 and 512 pods, and 257 / 256 / 129 /
+    128 / 65 / 64 around the boundaries of the one-, two-, four- and eight-group
+    kernel instances), bit-exact with the oracle; a 513-pod
     candidate exceeds the planner's per-candidate limit (MAX_CAND_PODS) and
     takes the fallback path.  The oracle plans every one of them."""
     from domain_cases import pod, term
     from test_gpu_parity import run_scenario
-    sizes = [511, 299, 256, 255, 64, 63]  # web pods; each candidate adds one db pod
+    sizes = [511, 299, 256, 255, 128, 127, 64, 63]  # web pods; each candidate adds one db pod
     big = [[pod("w%d" % i, "web", anti=[term("zone", "db")]) for i in range(n)] + [pod("d", "db")] for n in sizes]
     big.append([pod("w%d" % i, "web", anti=[term("zone", "db")]) for i in range(512)] + [pod("d", "db")])  # 513
     _, o, p = run_scenario(checker, nodes(), [[] for _ in range(4)], big, extra_fallback=lambda c: c == len(sizes))
