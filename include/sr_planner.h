@@ -513,7 +513,9 @@ const char *sr_build_info(void);
  * added sr_cluster.volumes and pod_stamp; ABI 6 the sr_timing enc_reused /
  * enc_pod_patches counters, which sr_get_timing writes; ABI 7 sr_timing.ms_collective; ABI 8
  * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields; ABI 10
- * sr_plan_sequence; ABI 11 sr_plan_sequence_pdb). */
+ * sr_plan_sequence; ABI 11 sr_plan_sequence_pdb; sr_explain_pods and
+ * sr_explain_candidate were added under ABI 11: two new functions, no struct
+ * changed its layout). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -532,6 +534,58 @@ sr_status sr_find_spot_nodes(sr_ctx *ctx, const sr_snapshot *snap, const sr_clus
 sr_status sr_can_drain_node(sr_ctx *ctx, sr_snapshot *snap, const sr_cluster *cluster,
                             const int32_t *pods, int32_t n, int32_t *out_node_of_pod,
                             int32_t *out_fail_pod, uint8_t *out_fallback);
+
+/* Why a pod fits no spot node: what the reference logs per node at
+ * rescheduler.go:348 (the error CheckPredicates returned), batched.  One bit
+ * per scheduler filter group, as far as the planner's factorisation of the
+ * filters can tell them apart.  The bits are not exclusive:
+ * every group is judged on its own against the snapshot as it stands, as
+ * kube-scheduler does when it runs all filters, and a node's mask holds every
+ * group that refuses the pod there.  Mask 0 is exactly "CheckPredicates
+ * returns nil".  NodeResourcesFit's bits follow fitsRequest [upstream k8s
+ * v1.19.2 noderesources/fit.go]: the pod count first; an all-zero request that
+ * lists no scalar sets none of CPU / MEMORY / EPHEMERAL; otherwise bit d is set
+ * iff allocatable_d < request_d + requested_d (also for a zero request in d on
+ * an over-committed node).  "The first failing filter" in the scheduler's
+ * filter order is the shim's to derive from the mask. */
+#define SR_WHY_UNSCHEDULABLE  (1u << 0)   /* NodeUnschedulable (Spec.Unschedulable, pseudo-taint not tolerated) */
+#define SR_WHY_TAINT          (1u << 1)   /* TaintToleration (an untolerated NoSchedule / NoExecute taint) */
+#define SR_WHY_NODE_AFFINITY  (1u << 2)   /* NodeAffinity: Spec.NodeSelector and required node affinity */
+#define SR_WHY_PODS           (1u << 3)   /* NodeResourcesFit: len(pods)+1 > allowed ("Too many pods") */
+#define SR_WHY_CPU            (1u << 4)   /* NodeResourcesFit: Insufficient cpu */
+#define SR_WHY_MEMORY         (1u << 5)   /*                   Insufficient memory */
+#define SR_WHY_EPHEMERAL      (1u << 6)   /*                   Insufficient ephemeral-storage */
+#define SR_WHY_SCALAR         (1u << 7)   /* NodeResourcesFit: the ScalarResources loop */
+#define SR_WHY_PORTS          (1u << 8)   /* NodePorts against the node's UsedPorts */
+#define SR_WHY_INTER_POD      (1u << 9)   /* InterPodAffinity: existing pods' anti-affinity, the pod's own anti-affinity, its affinity */
+#define SR_WHY_SPREAD         (1u << 10)  /* PodTopologySpread (DoNotSchedule) */
+#define SR_WHY_VOLUMES        (1u << 11)  /* the volume filters of sr_volumes (restrictions, limits, zone, binding, prefilter_fail) */
+#define SR_WHY_COUNT          12
+
+typedef struct {
+  int32_t  *feasible;   /* [n]  spot nodes with mask 0; -1 for a fallback pod */
+  int32_t  *first;      /* [n]  first spot position with mask 0 (= sr_find_spot_nodes), -1 none */
+  int32_t  *counts;     /* [n][SR_WHY_COUNT] nodes refusing for each reason (a node once per reason) */
+  uint16_t *node_mask;  /* optional [n][n_spot] the mask of every node; NULL = not wanted */
+  uint8_t  *fallback;   /* optional [n] 1: outside the encoded predicate set, nothing evaluated */
+} sr_explain_out;
+
+/* sr_find_spot_nodes with reasons: every pod judged against the snapshot as it
+ * is, on the device, in one call; the snapshot is not modified and nothing of
+ * the planning side (resident workloads, encoder state) is touched.  No
+ * collective, even with a communicator attached.  SR_ERR_INVALID_ARG for NULL
+ * handles, n < 0 or a NULL required output. */
+sr_status sr_explain_pods(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluster, const int32_t *pods,
+                          int32_t n, sr_explain_out *out);
+/* "Why did this candidate stop at pod at_pod": forks the snapshot, adds
+ * pods[0 .. at_pod) at node_of_pod[] (the mapping the plan returned,
+ * rescheduler.go:366), explains pods[at_pod] (out arrays sized for n = 1) and
+ * reverts.  SR_ERR_STATE on a forked snapshot; SR_ERR_INVALID_ARG also for
+ * at_pod outside [0, n) or a -1 / out-of-range position below at_pod; the
+ * snapshot is left unchanged on an argument error. */
+sr_status sr_explain_candidate(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
+                               const int32_t *pods, int32_t n, const int32_t *node_of_pod, int32_t at_pod,
+                               sr_explain_out *out);
 
 /* A batch of on-demand candidates in NodeInfoArray order (rescheduler.go:228),
  * each with its podsForDeletion list (rescheduler.go:231-256). */

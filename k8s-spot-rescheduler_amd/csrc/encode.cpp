@@ -42,6 +42,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "explain.hpp"
 #include "host.hpp"
 #include "pool.hpp"
 #include "worddict.hpp"
@@ -514,7 +515,7 @@ void draft_spec(const sr_cluster* c, int32_t pod, SpecDraft* d) {
   if (has_volume_spec(c, pod)) {
     const sr_volumes* V = c->volumes;
     // VolumeBinding PreFilter failing: the pod fits no node
-    if (V->prefilter_fail[pod]) d->flags |= CLS_IMPOSSIBLE;
+    if (V->prefilter_fail[pod]) d->flags |= CLS_IMPOSSIBLE | CLS_VOLUMES_DECIDE;
     // VolumeZone: each PV zone / region label a REQ_ZONE requirement
     for (int32_t z = V->zone_off[pod]; z < V->zone_off[pod + 1]; ++z) {
       std::vector<int32_t> vals(V->zone_vals + V->zone_val_off[z], V->zone_vals + V->zone_val_off[z + 1]);
@@ -545,7 +546,7 @@ void draft_spec(const sr_cluster* c, int32_t pod, SpecDraft* d) {
       }
       sel[0] = n_terms;
       if (n_terms == 0) {
-        d->flags |= CLS_IMPOSSIBLE;  // no term can match
+        d->flags |= CLS_IMPOSSIBLE | CLS_VOLUMES_DECIDE;  // no term can match
       } else if (n_terms == 1) {  // its requirements ANDed with the others
         d->vsel.insert(d->vsel.end(), sel.begin() + one + 1, sel.end());
         if (sel[one] == 0) continue;  // a term of decided fields only: every node
@@ -2474,7 +2475,16 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
     out.push_back(untol);
   };
   w->cls_prog_off.push_back(0);
-  auto emit = [&](int32_t atom, int32_t kind) { w->cls_prog.push_back(atom << 2 | kind); };
+  // `why`: the filter group the operation judges (explain.hpp), kept only for sr_explain_pods' encoder
+  const bool want_why = C.want_why;
+  auto emit = [&](int32_t atom, int32_t kind, int32_t why) {
+    w->cls_prog.push_back(atom << 2 | kind);
+    if (want_why) w->cls_why.push_back(static_cast<uint8_t>(why));
+  };
+  // a host-port query atom is NodePorts', an inline disk's pseudo port VolumeRestrictions'; a scalar query atom
+  // is the ScalarResources loop's, a volume limit key's (negative name) the volume limits'
+  auto port_why = [&](int32_t q) { return port_query[q].proto >= kDiskProto ? WHY_VOLUMES : WHY_PORTS; };
+  auto scalar_why = [&](int32_t q) { return scalar_query[q].first < 0 ? WHY_VOLUMES : WHY_SCALAR; };
   // program: AND atoms, AND-NOT atoms, then the ORed terms (TERM_START opens a
   // term, TERM_AND extends it); an impossible class ANDs atom 0 with its
   // complement.  `sw` = static signature words.
@@ -2493,28 +2503,36 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
     const int32_t* vpv = tp;
     tp += n_vpv;
     const int32_t untol = *tp;
-    emit(comp_atom(untol), PROG_AND);  // len(pods)+1 <= allowed pods, untolerated taints
-    for (int32_t k = 0; k < n_sel; ++k) emit(A_REQ + req_atom[sel[k]], PROG_AND);
-    for (int32_t k = 0; k < n_vsel; ++k) emit(A_REQ + req_atom[vsel[k]], PROG_AND);  // VolumeZone, PV affinity
-    for (int32_t k = 0; k < n_vpv; ++k) emit(A_VOL + pvsel_atom[vpv[k]], PROG_AND);
+    const int32_t comp = comp_atom(untol);
+    emit(comp, PROG_AND, comp == 0 ? WHY_PODS : WHY_COMPOSITE);  // len(pods)+1 <= allowed pods, untolerated taints
+    for (int32_t k = 0; k < n_sel; ++k) emit(A_REQ + req_atom[sel[k]], PROG_AND, WHY_NODE_AFFINITY);
+    for (int32_t k = 0; k < n_vsel; ++k)  // VolumeZone, PV affinity
+      emit(A_REQ + req_atom[vsel[k]], PROG_AND, WHY_VOLUMES);
+    for (int32_t k = 0; k < n_vpv; ++k) emit(A_VOL + pvsel_atom[vpv[k]], PROG_AND, WHY_VOLUMES);
     for (uint64_t m = ports; m; m &= m - 1) {  // the base UsedPorts conflicting with each host port it asks for
       const int32_t b = __builtin_ctzll(m);
-      if (bit_query[b] >= 0) emit(A_PORT + bit_query[b], PROG_ANDNOT);
+      if (bit_query[b] >= 0) emit(A_PORT + bit_query[b], PROG_ANDNOT, port_why(bit_query[b]));
     }
     if (sc_)
-      for (int32_t q : *sc_) emit(A_SCALAR + q, PROG_AND);  // alloc[s] >= request + requested[s]; spread rows
+      for (int32_t q : *sc_)  // alloc[s] >= request + requested[s]; spread rows
+        emit(A_SCALAR + q, PROG_AND, q >= n_scalars ? WHY_SPREAD : scalar_why(q));
     if (da_)
-      for (int32_t t : *da_) emit(A_ANTI + 2 * t, PROG_ANDNOT);  // anti-affinity base conflicts
+      for (int32_t t : *da_) emit(A_ANTI + 2 * t, PROG_ANDNOT, WHY_INTER_POD);  // anti-affinity base conflicts
     if (db_)
-      for (int32_t t : *db_) emit(A_ANTI + 2 * t + 1, PROG_ANDNOT);
-    if (aff_atom >= 0) emit(aff_atom, PROG_AND);
+      for (int32_t t : *db_) emit(A_ANTI + 2 * t + 1, PROG_ANDNOT, WHY_INTER_POD);
+    if (aff_atom >= 0) emit(aff_atom, PROG_AND, WHY_INTER_POD);
     if ((flags & CLS_IMPOSSIBLE) || aff_atom == -2) {
-      emit(0, PROG_ANDNOT);
+      // decided without rows: by a volume filter, else (CLS_IMPOSSIBLE) by a required node affinity without a
+      // valid term; by a pod affinity no node can satisfy
+      const int32_t vol = (flags & CLS_VOLUMES_DECIDE) ? WHY_DEC_VOLUMES : 0;
+      const bool no_term = (flags & CLS_AFF_REQUIRED) && n_terms == 0;
+      const int32_t node_aff = (flags & CLS_IMPOSSIBLE) && (!vol || no_term) ? WHY_DEC_NODE_AFFINITY : 0;
+      emit(0, PROG_ANDNOT, WHY_DECIDED | vol | node_aff | (aff_atom == -2 ? WHY_DEC_INTER_POD : 0));
     } else {
       for (int32_t k = 0; k < n_terms; ++k) {
         const int32_t n = *term_words++;
         for (int32_t i = 0; i < n; ++i)
-          emit(A_REQ + req_atom[term_words[i]], i == 0 ? PROG_TERM_START : PROG_TERM_AND);
+          emit(A_REQ + req_atom[term_words[i]], i == 0 ? PROG_TERM_START : PROG_TERM_AND, WHY_NODE_AFFINITY);
         term_words += n;
       }
     }
@@ -2611,6 +2629,12 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
   w->atoms.assign(static_cast<size_t>(w->n_atoms) * Wp, 0);
   uint64_t* A = w->atoms.data();
   std::copy(C.podcount_row.begin(), C.podcount_row.end(), A);
+  // the group of every row, where the row is made (sr_explain_pods' encoder only)
+  auto tag = [&](int32_t a0, int32_t n, int32_t why) {
+    if (want_why) std::fill_n(w->atom_why.begin() + a0, n, static_cast<uint8_t>(why));
+  };
+  if (want_why) w->atom_why.assign(static_cast<size_t>(w->n_atoms), WHY_NONE);
+  tag(0, 1, WHY_PODS);
   {
     if (C.req_rows.size() < C.req_dict.size()) {
       C.req_rows.resize(C.req_dict.size());
@@ -2639,6 +2663,10 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
     for (int32_t i = 0; i < n_reqs; ++i)
       std::copy(C.req_rows[used_reqs[i]].begin(), C.req_rows[used_reqs[i]].end(),
                 A + static_cast<size_t>(A_REQ + i) * Wp);
+    // a requirement row serves NodeAffinity and, named by a volume filter's operation, VolumeZone / VolumeBinding:
+    // the operation's own tag decides (Workload::cls_why)
+    tag(A_REQ, n_reqs, WHY_NODE_AFFINITY);
+    tag(A_VOL, static_cast<int32_t>(used_pvsel.size()), WHY_VOLUMES);
     // PV selectors: OR over the terms of the AND of their requirement rows
     for (size_t i = 0; i < used_pvsel.size(); ++i) {
       const int32_t* pw = C.pvsel_dict.data(used_pvsel[i]);
@@ -2657,6 +2685,16 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
     }
   }
   std::copy(C.taint_rows.begin(), C.taint_rows.end(), A + static_cast<size_t>(A_TAINT) * Wp);
+  for (int32_t t = 0; t < n_taints; ++t) {  // the pseudo-taint of Spec.Unschedulable is NodeUnschedulable's
+    const TaintRec& tr = C.taints[t];
+    const bool pseudo =
+        tr.key == snap->id_unschedulable_key && tr.val == snap->id_empty && tr.effect == SR_EFFECT_NO_SCHEDULE;
+    tag(A_TAINT + t, 1, pseudo ? WHY_UNSCHEDULABLE : WHY_TAINT);
+  }
+  for (int32_t q = 0; q < n_ports; ++q) tag(A_PORT + q, 1, port_why(q));
+  for (int32_t q = 0; q < n_scalars; ++q) tag(A_SCALAR + q, 1, scalar_why(q));
+  tag(A_SPREAD, n_spreads, WHY_SPREAD);
+  tag(A_ANTI, 2 * anti.n_terms + 2 * aff.n_sets, WHY_INTER_POD);
   if (n_ports > 0) port_conflict_rows(C, snap, port_query.data(), n_ports, Wp, A + static_cast<size_t>(A_PORT) * Wp);
   // NodeResourcesFit's ScalarResources loop against the base snapshot:
   // alloc[s] < request + requested[s] fails (a node without s allocates 0)
@@ -2695,6 +2733,16 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
     std::copy_n(&aff.keys[static_cast<size_t>(t) * Wp], Wp, A + static_cast<size_t>(A_AFF + 2 * t + 1) * Wp);
   }
   composite_rows(C, comp_sets, A_COMP, Wp, A);  // atom 0 AND NOT (any taint of the set)
+  if (want_why) {  // ... which an explain program takes apart again
+    tag(A_COMP, static_cast<int32_t>(comp_sets.size()), WHY_COMPOSITE);
+    w->comp_first = A_COMP;
+    w->comp_taint_off.assign(1, 0);
+    for (int32_t u : comp_sets) {
+      const int32_t* ts = C.untol_dict.data(u);
+      for (size_t j = 0; j < C.untol_dict.len(u); ++j) w->comp_taint_atom.push_back(A_TAINT + ts[j]);
+      w->comp_taint_off.push_back(static_cast<int32_t>(w->comp_taint_atom.size()));
+    }
+  }
   for (size_t k = 0; k < dk.key.size(); ++k)
     if (!dk.node_local[k])
       for (int32_t n = 0; n < n_spot; ++n)
@@ -2828,6 +2876,7 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
   w->pod_rec.resize(static_cast<size_t>(na + 128) * 6);  // padded: K2 stages 64-pod halves
   std::fill(w->pod_rec.begin() + static_cast<size_t>(na) * 6, w->pod_rec.end(), 0);
   w->pod_src = active_src;
+  if (want_why) w->pod_cls.resize(static_cast<size_t>(na));
   // Pods whose F row is certainly empty point at one all-zero class (atom 0
   // AND NOT atom 0), so K2 knows them without reading their rows: a class
   // that ANDs an empty atom, ANDs the complement of a full one, or whose
@@ -2855,6 +2904,7 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
       const int32_t ki = key_slot[pod_key[q]];
       int32_t* r = &w->pod_rows[q * 4];
       r[0] = key_class[ki];
+      if (want_why) w->pod_cls[q] = r[0];  // before the dead check: the class that says why
       r[1] = zero ? -1 : static_cast<int32_t>(lower(0, rc));
       r[2] = zero ? -1 : static_cast<int32_t>(lower(1, rm));
       r[3] = zero ? -1 : static_cast<int32_t>(lower(2, re));
@@ -2882,8 +2932,8 @@ sr_status encode_impl(EncoderCache& C, const sr_snapshot* snap, const sr_cluster
   });
   phase(10);
   if (any_dead.load(std::memory_order_relaxed) || want_index) {  // (a reuse encode may need it later)
-    emit(0, PROG_AND);
-    emit(0, PROG_ANDNOT);
+    emit(0, PROG_AND, WHY_PODS);
+    emit(0, PROG_ANDNOT, WHY_NONE);
     w->cls_prog_off.push_back(static_cast<int32_t>(w->cls_prog.size()));
     w->empty_class = w->n_classes++;
   }

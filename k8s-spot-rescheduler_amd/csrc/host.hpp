@@ -432,7 +432,9 @@ inline uint32_t pod_label_count(const sr_cluster* c, int32_t pod) {
 }
 
 // Class descriptor flags.
-enum : int32_t { CLS_AFF_REQUIRED = 1, CLS_IMPOSSIBLE = 2 };
+// CLS_VOLUMES_DECIDE: a volume filter made the class impossible (VolumeBinding's PreFilter, a bound PV whose node
+// affinity has no term that builds); without it the required node affinity did (no valid term).
+enum : int32_t { CLS_AFF_REQUIRED = 1, CLS_IMPOSSIBLE = 2, CLS_VOLUMES_DECIDE = 4 };
 
 // K2 domain path limits (antiaff.cpp, kernels.hip k2_domain)
 constexpr int kDomKeys = 4;   // key slots per encode
@@ -604,6 +606,12 @@ struct Workload {
   std::vector<int32_t> atom_rows;
   bool atom_rows_all = false;
   CandReuse reuse;                  // kept by reset(): the encoder rebuilds or drops it
+  // ---- reasons (explain.hpp), written only by an encode with EncoderCache::want_why (sr_explain_pods):
+  std::vector<uint8_t> atom_why;         // [n_atoms] the filter group each atom row belongs to
+  std::vector<uint8_t> cls_why;          // parallel to cls_prog: the group each operation judges
+  int32_t comp_first = 0;                // first composite atom
+  std::vector<int32_t> comp_taint_off, comp_taint_atom;  // CSR composite atom -> its set's taint atoms
+  std::vector<int32_t> pod_cls;          // [active pod] class before the dead check
 
   // Back to the default state, keeping every buffer's capacity: a planner
   // encodes one tick after another, and fresh multi-MB buffers page-fault.
@@ -637,6 +645,11 @@ struct Workload {
     pod_patch.clear();
     atom_cols.clear();
     tab_changed = false;
+    atom_why.clear();
+    cls_why.clear();
+    comp_taint_off.clear();
+    comp_taint_atom.clear();
+    pod_cls.clear();
   }
 };
 
@@ -675,6 +688,8 @@ struct EncoderCache {
                               //   512 instead of 1,024 -- C4 step 44.7 -> 42.6 us, C4 / affinity C4 latency -3 us)
   int32_t split_min = 4096;   // SR_K2_SPLIT_MIN: a work list with domain-path candidates and more entries than
                               //   this goes in two parts (planner.cpp k2_split)
+  bool want_why = false;      // the encoder of sr_explain_pods: every encode also tags atoms and class program
+                              //   operations with their filter group (Workload::atom_why, explain.hpp)
   int32_t id_empty = INT32_MIN, id_metadata_name = INT32_MIN, id_unschedulable_key = INT32_MIN;
   // ---- static view
   int32_t n_spot = -1, Wp = 0, n_pad = 0;

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "explain_dev.hpp"
 #include "host.hpp"
 #include "kernels.hpp"
 #include "residency.hpp"
@@ -196,6 +197,14 @@ struct sr_ctx {
   int32_t k2_excl = 1;        // SR_K2_EXCL: exclusive candidates (one host port) with the taken-mask step
   int32_t k2_node_kernel = 1; // SR_K2_NODE_KERNEL: node-order-only K2 kernel when every candidate takes that path
   int32_t s_head_only = 1;    // SR_S_HEAD_ONLY: K0 writes S-row heads only on rows wider than 64 words (0: never)
+  // sr_explain_pods: an encoder, a workload and buffers of its own, outside the slots, the workload arenas and
+  // the residency model, so a plan before and after an explain call encodes and uploads exactly the same
+  sr::EncoderCache x_enc;
+  sr::Workload x_wl;
+  sr::ExplainPrograms x_prog;
+  std::vector<sr::ExplainPod> x_pods;
+  DevBuf x_in, x_out;
+  HostBuf hx_in, hx_out;
 };
 
 namespace {
@@ -1416,7 +1425,7 @@ void sr_destroy(sr_ctx* ctx) {
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
                     &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off, &ctx->pdb_need, &ctx->pdb_remaining,
-                    &ctx->pdb_refused, &ctx->pdb_win})
+                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1425,7 +1434,7 @@ void sr_destroy(sr_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->out_cycles.p) (void)hipFree(ctx->out_cycles.p);
   for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm,
-                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb})
+                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb, &ctx->hx_in, &ctx->hx_out})
     if (b->p) (void)hipHostFree(b->p);
   for (auto& sl : ctx->slots) {
     if (sl->arena.p) (void)hipFree(sl->arena.p);
@@ -1804,6 +1813,132 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
   if (out_node_of_pod)
     for (int32_t i = 0; i < n; ++i) out_node_of_pod[i] = map[i];
   return SR_OK;
+}
+
+// sr_explain_pods.  Each pod is a candidate of its own, encoded by the
+// context's explain encoder (x_enc: tags on), so a pod has no earlier pod of
+// its candidate and every filter is a static atom.  The call uploads what its
+// kernel reads -- the atom rows, the node free values of this encode, the
+// explain programs, the pods -- into one buffer of its own; nothing of the
+// planning side is read, written or re-encoded.
+static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
+                         sr_explain_out* out) {
+  if (n == 0) return SR_OK;
+  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
+  for (int32_t i = 0; i <= n; ++i) off[i] = i;
+  const sr_candidates cands{n, off.data(), pods, nullptr};
+  sr::Workload& w = ctx->x_wl;
+  ctx->x_enc.want_why = true;
+  w.reuse.drop();  // always a full encode: the tags belong to it
+  std::string err;
+  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &cands, &w, &err);
+  if (st != SR_OK) {
+    ctx->err = err;
+    return st;
+  }
+  const int32_t n_spot = w.n_spot, na = static_cast<int32_t>(w.pod_src.size());
+  const size_t ns = static_cast<size_t>(n_spot);
+  for (int32_t i = 0; i < n; ++i) {  // a fallback pod: nothing evaluated
+    const bool fb = w.status_host[i] == SR_CAND_FALLBACK;
+    out->feasible[i] = out->first[i] = -1;
+    std::fill_n(out->counts + static_cast<size_t>(i) * SR_WHY_COUNT, SR_WHY_COUNT, 0);
+    if (out->node_mask) std::fill_n(out->node_mask + i * ns, ns, uint16_t(0));
+    if (out->fallback) out->fallback[i] = fb ? 1 : 0;
+  }
+  if (na == 0) return SR_OK;
+  if (!sr::build_explain(w, &ctx->x_prog) || w.pod_cls.size() != static_cast<size_t>(na) || w.n_pad != w.Wp * 64 ||
+      ctx->x_enc.node_free.size() < 3 * static_cast<size_t>(w.n_pad)) {
+    ctx->err = "explain: the encoder left no reasons";
+    return SR_ERR_STATE;
+  }
+  sr::explain_pods(w, &ctx->x_pods);
+  for (const sr::ExplainPod& p : ctx->x_pods)
+    if (p.cls < 0 || p.cls >= w.n_classes) {
+      ctx->err = "explain: pod class out of range";
+      return SR_ERR_STATE;
+    }
+  for (int32_t op : ctx->x_prog.ops)  // what the kernel indexes with
+    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > sr::X_ALL) {
+      ctx->err = "explain: malformed program";
+      return SR_ERR_STATE;
+    }
+  // input: atoms | node_free | xoff | xops | pods (8-byte aligned parts)
+  auto up8 = [](size_t b) { return (b + 7) & ~size_t(7); };
+  const size_t b_atoms = w.atoms.size() * sizeof(uint64_t), b_free = 3 * static_cast<size_t>(w.n_pad) * sizeof(int64_t);
+  const size_t b_off = up8(ctx->x_prog.off.size() * sizeof(int32_t)), b_ops = up8(ctx->x_prog.ops.size() * sizeof(int32_t));
+  const size_t b_pods = static_cast<size_t>(na) * sizeof(sr::ExplainPod);
+  const size_t o_free = b_atoms, o_off = o_free + b_free, o_ops = o_off + b_off, o_pods = o_ops + b_ops;
+  const size_t in_bytes = o_pods + b_pods;
+  const size_t b_sums = static_cast<size_t>(na) * sr::kExplainSums * sizeof(int32_t);
+  const size_t out_bytes = b_sums + (out->node_mask ? static_cast<size_t>(na) * ns * sizeof(uint16_t) : 0);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
+  HIP_TRY(ctx, host_reserve(ctx->hx_in, in_bytes));
+  HIP_TRY(ctx, host_reserve(ctx->hx_out, out_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_in, in_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_out, out_bytes));
+  char* h = static_cast<char*>(ctx->hx_in.p);
+  std::memcpy(h, w.atoms.data(), b_atoms);
+  std::memcpy(h + o_free, ctx->x_enc.node_free.data(), b_free);
+  std::memcpy(h + o_off, ctx->x_prog.off.data(), ctx->x_prog.off.size() * sizeof(int32_t));
+  std::memcpy(h + o_ops, ctx->x_prog.ops.data(), ctx->x_prog.ops.size() * sizeof(int32_t));
+  std::memcpy(h + o_pods, ctx->x_pods.data(), b_pods);
+  char* d = static_cast<char*>(ctx->x_in.p);
+  HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, b_sums, ctx->stream));
+  sr::ExplainArgs a{};
+  a.n_spot = n_spot;
+  a.n_pad = w.n_pad;
+  a.Wp = w.Wp;
+  a.n_pods = na;
+  a.atoms = reinterpret_cast<const uint64_t*>(d);
+  a.node_free = reinterpret_cast<const int64_t*>(d + o_free);
+  a.xoff = reinterpret_cast<const int32_t*>(d + o_off);
+  a.xops = reinterpret_cast<const int32_t*>(d + o_ops);
+  a.pods = reinterpret_cast<const sr::ExplainPod*>(d + o_pods);
+  a.sums = static_cast<int32_t*>(ctx->x_out.p);
+  a.node_mask = out->node_mask ? reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->x_out.p) + b_sums) : nullptr;
+  HIP_TRY(ctx, sr::launch_explain(a, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t* sums = static_cast<const int32_t*>(ctx->hx_out.p);
+  const uint16_t* masks = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->hx_out.p) + b_sums);
+  for (int32_t q = 0; q < na; ++q) {
+    const int32_t i = w.pod_src[q] - w.pod_base;
+    const int32_t* s = sums + static_cast<size_t>(q) * sr::kExplainSums;
+    std::copy_n(s, SR_WHY_COUNT, out->counts + static_cast<size_t>(i) * SR_WHY_COUNT);
+    out->feasible[i] = s[sr::kExplainFeasible];
+    out->first[i] = s[sr::kExplainFirst] > 0 ? w.n_pad - s[sr::kExplainFirst] : -1;
+    if (out->node_mask) std::copy_n(masks + q * ns, ns, out->node_mask + i * ns);
+  }
+  return SR_OK;
+}
+
+static bool explain_out_ok(const sr_explain_out* out) { return out && out->feasible && out->first && out->counts; }
+
+sr_status sr_explain_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
+                          sr_explain_out* out) {
+  if (!ctx || !snap || !cluster || n < 0 || !explain_out_ok(out) || (n > 0 && !pods)) return SR_ERR_INVALID_ARG;
+  return explain(ctx, snap, cluster, pods, n, out);
+}
+
+sr_status sr_explain_candidate(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
+                               const int32_t* node_of_pod, int32_t at_pod, sr_explain_out* out) {
+  if (!ctx || !snap || !cluster || n < 0 || !explain_out_ok(out) || !pods || !node_of_pod) return SR_ERR_INVALID_ARG;
+  if (snap->forked) return SR_ERR_STATE;
+  if (at_pod < 0 || at_pod >= n) return SR_ERR_INVALID_ARG;
+  const int32_t n_spot = static_cast<int32_t>(snap->nodes.size());
+  for (int32_t k = 0; k <= at_pod; ++k)
+    if (pods[k] < 0 || pods[k] >= cluster->pods.n || (k < at_pod && (node_of_pod[k] < 0 || node_of_pod[k] >= n_spot)))
+      return SR_ERR_INVALID_ARG;
+  // Fork; the earlier pods where the plan put them (rescheduler.go:366): base
+  // pods now, so what they do to pods[at_pod] is static atoms; Revert
+  sr_status st = sr_snapshot_fork(snap);
+  if (st != SR_OK) return st;
+  for (int32_t k = 0; k < at_pod; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], node_of_pod[k]);
+  st = explain(ctx, snap, cluster, pods + at_pod, 1, out);
+  const sr_status rv = sr_snapshot_revert(snap);
+  return st != SR_OK ? st : rv;
 }
 
 sr_status sr_set_timing(sr_ctx* ctx, int32_t mask) {

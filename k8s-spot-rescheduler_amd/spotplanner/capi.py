@@ -173,6 +173,20 @@ class sr_pdb_limits(_KeepsArrays):
     _fields_ = [("n_groups", ctypes.c_int32), ("allowed", P32), ("pod_group", P32), ("remaining", P32)]
 
 
+PU16 = ctypes.POINTER(ctypes.c_uint16)
+
+
+class sr_explain_out(_KeepsArrays):
+    _fields_ = [("feasible", P32), ("first", P32), ("counts", P32), ("node_mask", PU16), ("fallback", PU8)]
+
+
+# The reasons of sr_explain_pods in bit order: WHY_NAMES[r] is bit 1 << r (SR_WHY_<name>).
+WHY_NAMES = ["UNSCHEDULABLE", "TAINT", "NODE_AFFINITY", "PODS", "CPU", "MEMORY", "EPHEMERAL", "SCALAR", "PORTS",
+             "INTER_POD", "SPREAD", "VOLUMES"]
+assert len(WHY_NAMES) == SR_WHY_COUNT  # noqa: F821 (parsed from the header)
+assert all(_DEF["SR_WHY_" + name] == 1 << r for r, name in enumerate(WHY_NAMES))
+
+
 # sr_allreduce_min_fn: int32 fn(void *user, uint64_t *words, int32_t n)
 ALLREDUCE_MIN_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32)
 
@@ -386,6 +400,11 @@ def _declare_planner(lib):
     lib.sr_find_spot_nodes.restype = S
     lib.sr_can_drain_node.argtypes = [VP, VP, PC, P32, ctypes.c_int32, P32, P32, PU8]
     lib.sr_can_drain_node.restype = S
+    lib.sr_explain_pods.argtypes = [VP, VP, PC, P32, ctypes.c_int32, ctypes.POINTER(sr_explain_out)]
+    lib.sr_explain_pods.restype = S
+    lib.sr_explain_candidate.argtypes = [VP, VP, PC, P32, ctypes.c_int32, P32, ctypes.c_int32,
+                                         ctypes.POINTER(sr_explain_out)]
+    lib.sr_explain_candidate.restype = S
     lib.sr_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
     lib.sr_plan.restype = S
     lib.sr_plan_first.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
@@ -420,7 +439,8 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_destroy",
             "sr_snapshot_add_pod", "sr_snapshot_fork", "sr_snapshot_revert", "sr_snapshot_node_state",
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
-            "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_plan", "sr_plan_first", "sr_plan_sequence",
+            "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_explain_pods", "sr_explain_candidate",
+            "sr_plan", "sr_plan_first", "sr_plan_sequence",
             "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",
             "sr_comm_init_shm"]

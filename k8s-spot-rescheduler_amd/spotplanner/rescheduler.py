@@ -5,6 +5,8 @@ validateArgs (:407-417), podID (:402-404), and plan_arrays: the planning
 segment of run() (:228-287) evaluated for every candidate at once on the GPU.
 plan_sequence_arrays / drainSequence go beyond the reference, which drains one
 node per tick: several consistent drains planned in one tick (sr_plan_sequence).
+explainPods / explainCandidate batch the per-node log line of :348: which filter
+groups refuse a pod on each spot node (sr_explain_pods).
 """
 from __future__ import annotations
 
@@ -299,3 +301,89 @@ def drainSequence(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnaps
             p.node_name = ""  # :341
         plans.append((int(c), [nodes[int(k)].Node.name for k in seg]))
     return r, plans
+
+
+@dataclass
+class ExplainResult:
+    """sr_explain_out for n pods: why each pod is refused on the spot nodes (capi.SR_WHY_* bits)."""
+    feasible: np.ndarray             # [n] spot nodes with mask 0; -1 for a fallback pod
+    first: np.ndarray                # [n] first spot position with mask 0 (findSpotNodeForPod), -1 none
+    counts: np.ndarray               # [n][SR_WHY_COUNT] nodes refusing for each reason
+    fallback: np.ndarray             # [n] 1: outside the encoded predicate set, nothing evaluated
+    node_mask: Optional[np.ndarray]  # [n][n_spot] the mask of every node (None: not asked for)
+    n_spot: int = 0
+
+    def reasons(self, i: int = 0) -> dict:
+        """{reason name: nodes refusing for it} of pod i, reasons no node gives left out."""
+        return {name: int(k) for name, k in zip(capi.WHY_NAMES, self.counts[i]) if k}
+
+    def summary(self, i: int = 0) -> str:
+        """The scheduler's line: "0/3 nodes are available: 2 CPU, 1 TAINT." """
+        n_spot = self.n_spot
+        why = ", ".join("%d %s" % (k, name) for name, k in self.reasons(i).items())
+        return "%d/%d nodes are available%s." % (max(int(self.feasible[i]), 0), n_spot, ": " + why if why else "")
+
+
+def _explain_out(n: int, n_spot: int, node_mask: bool):
+    feasible = np.full(max(n, 1), -1, np.int32)
+    first = np.full(max(n, 1), -1, np.int32)
+    counts = np.zeros((max(n, 1), capi.SR_WHY_COUNT), np.int32)
+    fallback = np.zeros(max(n, 1), np.uint8)
+    masks = np.zeros((max(n, 1), max(n_spot, 1)), np.uint16) if node_mask else None
+    # the struct keeps the pointers it is given, and they their arrays (capi._KeepsArrays)
+    o = capi.sr_explain_out(capi.ptr(feasible, capi.P32), capi.ptr(first, capi.P32), capi.ptr(counts, capi.P32),
+                            capi.ptr(masks, capi.PU16) if node_mask else None, capi.ptr(fallback, capi.PU8))
+    res = ExplainResult(feasible[:n], first[:n], counts[:n], fallback[:n], masks[:n, :n_spot] if node_mask else None,
+                        n_spot)
+    return o, res
+
+
+def explain_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, pods: np.ndarray,
+                   node_mask: bool = True) -> ExplainResult:
+    """sr_explain_pods over caller-built arrays: every pod judged against the snapshot as it is."""
+    lib = predicateChecker.lib
+    pods = np.ascontiguousarray(pods, np.int32)
+    o, res = _explain_out(len(pods), lib.sr_snapshot_num_nodes(snapshot_handle), node_mask)
+    st = lib.sr_explain_pods(predicateChecker.handle, snapshot_handle, cluster_ptr, capi.ptr(pods, capi.P32), len(pods),
+                             ctypes.byref(o))
+    if st != capi.SR_OK:
+        raise PlannerError("sr_explain_pods: %d %s" % (st, predicateChecker.last_error()))
+    return res
+
+
+def explain_candidate_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, pods: np.ndarray,
+                             node_of_pod: np.ndarray, at_pod: int, node_mask: bool = True) -> ExplainResult:
+    """sr_explain_candidate: pods[at_pod] explained with pods[:at_pod] added at node_of_pod (the plan's mapping);
+    the snapshot is restored."""
+    lib = predicateChecker.lib
+    pods = np.ascontiguousarray(pods, np.int32)
+    node_of_pod = np.ascontiguousarray(node_of_pod, np.int32)
+    o, res = _explain_out(1, lib.sr_snapshot_num_nodes(snapshot_handle), node_mask)
+    st = lib.sr_explain_candidate(predicateChecker.handle, snapshot_handle, cluster_ptr, capi.ptr(pods, capi.P32),
+                                  len(pods), capi.ptr(node_of_pod, capi.P32), int(at_pod), ctypes.byref(o))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_explain_candidate: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    return res
+
+
+def explainPods(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes, pods: Sequence[Pod],
+                node_mask: bool = True) -> ExplainResult:
+    """What the reference logs per spot node at rescheduler.go:348, for every pod at once."""
+    _check_order(spotSnapshot, nodes)
+    enc = spotSnapshot.encode_pods(list(pods))
+    return explain_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, np.arange(len(pods), dtype=np.int32),
+                          node_mask)
+
+
+def explainCandidate(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes, pods: Sequence[Pod],
+                     mapping: Sequence[str], at_pod: int, node_mask: bool = True) -> ExplainResult:
+    """Why canDrainNode stopped at pods[at_pod]: `mapping` is the spot node name of every earlier pod
+    (canDrainNode.last_mapping)."""
+    _check_order(spotSnapshot, nodes)
+    enc = spotSnapshot.encode_pods(list(pods))
+    pos = {name: i for i, name in enumerate(_node_names(nodes))}
+    node_of_pod = np.array([pos.get(mapping[k], -1) if k < at_pod else -1 for k in range(len(pods))], np.int32)
+    return explain_candidate_arrays(predicateChecker, spotSnapshot.handle, enc.ptr,
+                                    np.arange(len(pods), dtype=np.int32), node_of_pod, at_pod, node_mask)
