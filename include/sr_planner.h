@@ -515,7 +515,7 @@ const char *sr_build_info(void);
  * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields; ABI 10
  * sr_plan_sequence; ABI 11 sr_plan_sequence_pdb; sr_explain_pods and
  * sr_explain_candidate were added under ABI 11: two new functions, no struct
- * changed its layout). */
+ * changed its layout; sr_explain_plan likewise: one more function). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -622,6 +622,32 @@ typedef struct {
  * Revert), all in parallel on the GPU.  The snapshot is not modified. */
 sr_status sr_plan(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluster,
                   const sr_candidates *cands, sr_plan_out *out);
+
+/* "Why did every stuck candidate of this tick stop": sr_explain_candidate for
+ * a whole plan in one call.  at_pod[c] is the pod of candidate c to explain,
+ * as an index into c's list, or negative for "not this candidate":
+ * sr_plan_out.status can be passed as it is, and a placed pod may be asked for
+ * too.  node_of_pod is sr_plan_out.node_of_pod (parallel to cand_pods,
+ * relative to cand_pod_off[0]); only entries below at_pod[c] are read.  Every
+ * array of `out` is indexed by the candidate's local position ([n_cand],
+ * [n_cand][SR_WHY_COUNT], [n_cand][n_spot]); cand_global is ignored.  For every
+ * asked candidate the result is sr_explain_candidate's for (its pods, its part
+ * of node_of_pod, at_pod[c]).  Candidates whose earlier pods change nothing for
+ * the stop pod but the touched nodes' pod count and requested cpu / memory /
+ * ephemeral are explained together by one device pass against
+ * the snapshot as it is; the others one at a time through Fork / AddPod /
+ * Revert.  out_how[c] says which.  SR_ERR_INVALID_ARG: NULL handles or required
+ * outputs, at_pod[c] >= the pods of c, a pod index out of range, a position
+ * below at_pod[c] that is -1 or >= the spot nodes; SR_ERR_STATE on a forked
+ * snapshot.  Arguments are checked before the first Fork: an argument error
+ * leaves the snapshot untouched, and it is restored on every other path.  No
+ * collective, as for sr_explain_pods. */
+#define SR_EXPLAIN_NONE    0  /* at_pod[c] < 0: nothing asked, outputs as for a fallback pod but fallback = 0 */
+#define SR_EXPLAIN_BATCHED 1  /* explained by the batched device pass */
+#define SR_EXPLAIN_SINGLE  2  /* explained one candidate at a time (Fork / AddPod / explain / Revert) */
+sr_status sr_explain_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
+                          const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
+                          sr_explain_out *out, uint8_t *out_how /* optional [n_cand] */);
 
 /* The planning segment as run() executes it (rescheduler.go:228-287): the
  * candidates in order until the first whose plan succeeds (drain + break,

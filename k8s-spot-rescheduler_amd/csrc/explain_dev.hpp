@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "explain.hpp"
+#include "explain_plan.hpp"
 
 namespace sr {
 
@@ -30,5 +31,16 @@ struct ExplainArgs {
 };
 
 hipError_t launch_explain(const ExplainArgs& a, hipStream_t s);
+
+// sr_explain_plan (explain_plan.hip): the same, a query being a candidate's
+// stop pod with the plain context of its earlier pods, from the same buffer.
+struct ExplainPlanArgs {
+  ExplainArgs x;
+  const int32_t* ctx_off;       // [n_pods + 1] CSR query -> entries
+  const PlanCtxEntry* ctx;      // per query sorted by node, nodes < n_spot
+  const int32_t* node_slack;    // [n_pad] allowed pods - pods, pads 0
+};
+
+hipError_t launch_explain_plan(const ExplainPlanArgs& a, hipStream_t s);
 
 }  // namespace sr

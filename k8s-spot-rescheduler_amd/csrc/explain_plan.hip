@@ -1,0 +1,88 @@
+// explain_plan.hip — per-node refusal reasons of a candidate's stop pod in the context of its earlier
+// pods (sr_explain_plan, gfx950).
+//
+// The grid of explain.hip: blockIdx.y is the query, a block of four waves
+// takes four 64-bit row words, a lane one node, and the program walk is the
+// same code (explain_walk.hpp).  A query carries the plain context of its
+// earlier pods (explain_plan.hpp): a list sorted by node of {node, pods, acc[3]}.
+// The entries of a wave's own word lie contiguously in it; the wave finds the
+// first with a wave-uniform binary search and walks them with wave-uniform
+// loads, and the lane owning an entry's node keeps it.  On such a touched node
+// PODS is slack - pods < 1 (replacing the bit the atom-0 row gave) and CPU /
+// MEMORY / EPHEMERAL compare the request with free - acc; every other bit
+// stays as the walk left it.  A query with an empty list costs what k_explain
+// costs and two more scalar loads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "explain_dev.hpp"
+#include "explain_walk.hpp"
+
+namespace sr {
+
+namespace {
+
+__global__ __launch_bounds__(kXThreads) void k_explain_plan(ExplainPlanArgs pa) {
+  __shared__ int s_part[kXWaves][kXCols];
+  const ExplainArgs& a = pa.x;
+  const int q = a.pod0 + static_cast<int>(blockIdx.y);
+  const int lane = static_cast<int>(threadIdx.x) & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  const int word = static_cast<int>(blockIdx.x) * kXWaves + wave;
+  const bool live = word < a.Wp;  // (wave-uniform; every wave reaches the barrier of explain_reduce)
+  const int node = word * 64 + lane;
+  const bool valid = live && node < a.n_spot;
+  uint32_t mask = 0;
+  if (live) {
+    const ExplainPod p = a.pods[q];
+    bool pods_judged;
+    mask = explain_walk(a, p.cls, word, lane, &pods_judged);
+    // the context entries of this word: [first entry with node >= 64 word, first with node >= 64 (word + 1))
+    const int c0 = pa.ctx_off[q], c1 = pa.ctx_off[q + 1];
+    int touched = 0;  // earlier pods on the lane's node
+    int64_t acc[3] = {0, 0, 0};
+    if (c0 < c1) {
+      int lo = c0, hi = c1;
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (pa.ctx[mid].node < word * 64) lo = mid + 1;
+        else hi = mid;
+      }
+      for (int i = lo; i < c1; ++i) {
+        const int en = pa.ctx[i].node;
+        if (en >= word * 64 + 64) break;
+        if (en == node) {
+          touched = pa.ctx[i].pods;
+          for (int d = 0; d < 3; ++d) acc[d] = pa.ctx[i].acc[d];
+        }
+      }
+    }
+    if (touched > 0 && pods_judged)
+      mask = (mask & ~(1u << WHY_PODS)) | (pa.node_slack[node] - touched < 1 ? 1u << WHY_PODS : 0u);
+    if (p.resources) {  // node < n_pad = 64 Wp: the pads hold INT64_MIN, are never touched and are cleared below
+      for (int d = 0; d < 3; ++d)
+        if (p.req[d] > a.node_free[static_cast<size_t>(d) * a.n_pad + node] - acc[d]) mask |= 1u << (WHY_CPU + d);
+    }
+    if (!valid) mask = 0;
+    if (a.node_mask && valid) a.node_mask[static_cast<size_t>(q) * a.n_spot + node] = static_cast<uint16_t>(mask);
+  }
+  explain_reduce(s_part, mask, valid, word, lane, wave, a.n_pad, a.sums + static_cast<size_t>(q) * kExplainSums);
+}
+
+}  // namespace
+
+hipError_t launch_explain_plan(const ExplainPlanArgs& a, hipStream_t s) {
+  const unsigned gx = static_cast<unsigned>((a.x.Wp + kXWaves - 1) / kXWaves);
+  for (int32_t q0 = 0; q0 < a.x.n_pods; q0 += 65535) {  // (gridDim.y)
+    ExplainPlanArgs part = a;
+    part.x.pod0 = q0;
+    hipLaunchKernelGGL(k_explain_plan, dim3(gx, static_cast<unsigned>(std::min(65535, a.x.n_pods - q0))),
+                       dim3(kXThreads), 0, s, part);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace sr

@@ -203,6 +203,9 @@ struct sr_ctx {
   sr::Workload x_wl;
   sr::ExplainPrograms x_prog;
   std::vector<sr::ExplainPod> x_pods;
+  std::vector<sr::PlanCtxEntry> x_centries;  // sr_explain_plan: the context lists, their offsets and the nodes'
+                                             //   pod slack as the kernel reads them
+  std::vector<int32_t> x_coff, x_slack;
   DevBuf x_in, x_out;
   HostBuf hx_in, hx_out;
 };
@@ -1821,8 +1824,12 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
 // kernel reads -- the atom rows, the node free values of this encode, the
 // explain programs, the pods -- into one buffer of its own; nothing of the
 // planning side is read, written or re-encoded.
+// sr_explain_plan's batched pass is the same call with `pq`: pods are its
+// stop pods, pod i carries the context list pq->off[i] and the kernel is
+// explain_plan.hip's, which reads the lists and the nodes' pod slack from the
+// same buffer.  `slot` (nullptr: i) is where pod i's results go in `out`.
 static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                         sr_explain_out* out) {
+                         sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr) {
   if (n == 0) return SR_OK;
   std::vector<int32_t> off(static_cast<size_t>(n) + 1);
   for (int32_t i = 0; i <= n; ++i) off[i] = i;
@@ -1840,10 +1847,11 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   const size_t ns = static_cast<size_t>(n_spot);
   for (int32_t i = 0; i < n; ++i) {  // a fallback pod: nothing evaluated
     const bool fb = w.status_host[i] == SR_CAND_FALLBACK;
-    out->feasible[i] = out->first[i] = -1;
-    std::fill_n(out->counts + static_cast<size_t>(i) * SR_WHY_COUNT, SR_WHY_COUNT, 0);
-    if (out->node_mask) std::fill_n(out->node_mask + i * ns, ns, uint16_t(0));
-    if (out->fallback) out->fallback[i] = fb ? 1 : 0;
+    const size_t o = static_cast<size_t>(slot ? slot[i] : i);
+    out->feasible[o] = out->first[o] = -1;
+    std::fill_n(out->counts + o * SR_WHY_COUNT, SR_WHY_COUNT, 0);
+    if (out->node_mask) std::fill_n(out->node_mask + o * ns, ns, uint16_t(0));
+    if (out->fallback) out->fallback[o] = fb ? 1 : 0;
   }
   if (na == 0) return SR_OK;
   if (!sr::build_explain(w, &ctx->x_prog) || w.pod_cls.size() != static_cast<size_t>(na) || w.n_pad != w.Wp * 64 ||
@@ -1862,13 +1870,35 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
       ctx->err = "explain: malformed program";
       return SR_ERR_STATE;
     }
-  // input: atoms | node_free | xoff | xops | pods (8-byte aligned parts)
+  // input: atoms | node_free | xoff | xops | pods [| context entries | context offsets | node slack] (8-byte
+  // aligned parts)
   auto up8 = [](size_t b) { return (b + 7) & ~size_t(7); };
   const size_t b_atoms = w.atoms.size() * sizeof(uint64_t), b_free = 3 * static_cast<size_t>(w.n_pad) * sizeof(int64_t);
   const size_t b_off = up8(ctx->x_prog.off.size() * sizeof(int32_t)), b_ops = up8(ctx->x_prog.ops.size() * sizeof(int32_t));
   const size_t b_pods = static_cast<size_t>(na) * sizeof(sr::ExplainPod);
   const size_t o_free = b_atoms, o_off = o_free + b_free, o_ops = o_off + b_off, o_pods = o_ops + b_ops;
-  const size_t in_bytes = o_pods + b_pods;
+  size_t b_ctx = 0, b_coff = 0, b_slack = 0;
+  if (pq) {  // the lists in active-pod order
+    ctx->x_coff.assign(1, 0);
+    ctx->x_centries.clear();
+    for (int32_t q = 0; q < na; ++q) {
+      const int32_t i = w.pod_src[q] - w.pod_base;
+      const auto e0 = pq->entries.begin();
+      ctx->x_centries.insert(ctx->x_centries.end(), e0 + pq->off[i], e0 + pq->off[i + 1]);
+      ctx->x_coff.push_back(static_cast<int32_t>(ctx->x_centries.size()));
+    }
+    for (const sr::PlanCtxEntry& e : ctx->x_centries)  // what the kernel indexes with
+      if (e.node < 0 || e.node >= n_spot) {
+        ctx->err = "explain: context node out of range";
+        return SR_ERR_STATE;
+      }
+    sr::node_slack(snap, w.n_pad, &ctx->x_slack);
+    b_ctx = ctx->x_centries.size() * sizeof(sr::PlanCtxEntry);
+    b_coff = up8(ctx->x_coff.size() * sizeof(int32_t));
+    b_slack = up8(ctx->x_slack.size() * sizeof(int32_t));
+  }
+  const size_t o_ctx = o_pods + b_pods, o_coff = o_ctx + b_ctx, o_slack = o_coff + b_coff;
+  const size_t in_bytes = o_slack + b_slack;
   const size_t b_sums = static_cast<size_t>(na) * sr::kExplainSums * sizeof(int32_t);
   const size_t out_bytes = b_sums + (out->node_mask ? static_cast<size_t>(na) * ns * sizeof(uint16_t) : 0);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1883,6 +1913,11 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   std::memcpy(h + o_off, ctx->x_prog.off.data(), ctx->x_prog.off.size() * sizeof(int32_t));
   std::memcpy(h + o_ops, ctx->x_prog.ops.data(), ctx->x_prog.ops.size() * sizeof(int32_t));
   std::memcpy(h + o_pods, ctx->x_pods.data(), b_pods);
+  if (pq) {
+    if (b_ctx) std::memcpy(h + o_ctx, ctx->x_centries.data(), b_ctx);
+    std::memcpy(h + o_coff, ctx->x_coff.data(), ctx->x_coff.size() * sizeof(int32_t));
+    std::memcpy(h + o_slack, ctx->x_slack.data(), ctx->x_slack.size() * sizeof(int32_t));
+  }
   char* d = static_cast<char*>(ctx->x_in.p);
   HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, b_sums, ctx->stream));
@@ -1898,15 +1933,25 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   a.pods = reinterpret_cast<const sr::ExplainPod*>(d + o_pods);
   a.sums = static_cast<int32_t*>(ctx->x_out.p);
   a.node_mask = out->node_mask ? reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->x_out.p) + b_sums) : nullptr;
-  HIP_TRY(ctx, sr::launch_explain(a, ctx->stream));
+  if (pq) {
+    sr::ExplainPlanArgs pa{};
+    pa.x = a;
+    pa.ctx = reinterpret_cast<const sr::PlanCtxEntry*>(d + o_ctx);
+    pa.ctx_off = reinterpret_cast<const int32_t*>(d + o_coff);
+    pa.node_slack = reinterpret_cast<const int32_t*>(d + o_slack);
+    HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
+  } else {
+    HIP_TRY(ctx, sr::launch_explain(a, ctx->stream));
+  }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const int32_t* sums = static_cast<const int32_t*>(ctx->hx_out.p);
   const uint16_t* masks = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->hx_out.p) + b_sums);
   for (int32_t q = 0; q < na; ++q) {
-    const int32_t i = w.pod_src[q] - w.pod_base;
+    const int32_t src = w.pod_src[q] - w.pod_base;
+    const size_t i = static_cast<size_t>(slot ? slot[src] : src);
     const int32_t* s = sums + static_cast<size_t>(q) * sr::kExplainSums;
-    std::copy_n(s, SR_WHY_COUNT, out->counts + static_cast<size_t>(i) * SR_WHY_COUNT);
+    std::copy_n(s, SR_WHY_COUNT, out->counts + i * SR_WHY_COUNT);
     out->feasible[i] = s[sr::kExplainFeasible];
     out->first[i] = s[sr::kExplainFirst] > 0 ? w.n_pad - s[sr::kExplainFirst] : -1;
     if (out->node_mask) std::copy_n(masks + q * ns, ns, out->node_mask + i * ns);
@@ -1939,6 +1984,54 @@ sr_status sr_explain_candidate(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster*
   st = explain(ctx, snap, cluster, pods + at_pod, 1, out);
   const sr_status rv = sr_snapshot_revert(snap);
   return st != SR_OK ? st : rv;
+}
+
+// sr_explain_plan.  The plain contexts (explain_plan.hpp) go through one
+// encode of their stop pods against the base snapshot, one upload, one launch
+// and one download; every other asked candidate through Fork / AddPod /
+// explain / Revert, as sr_explain_candidate does it.  A stop pod the batched
+// encode hands back as fallback is asked again on its own when the batch held
+// other pods: candidates of one encode share the state word's host-port bits,
+// so only an encode of its own tells "outside the encoded set" for certain.
+sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                          const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how) {
+  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !explain_out_ok(out)) return SR_ERR_INVALID_ARG;
+  const int32_t nc = cands->n_cand;
+  if (nc > 0 && (!cands->cand_pod_off || !cands->cand_pods || !at_pod)) return SR_ERR_INVALID_ARG;
+  if (snap->forked) return SR_ERR_STATE;
+  // (the queries are built apart from the context: an argument error returns before the context is looked at)
+  sr::PlanQueries pq;
+  sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
+  if (st != SR_OK) return st;
+  const size_t ns = snap->nodes.size();
+  for (int32_t c = 0; c < nc; ++c) {  // not asked: as a fallback pod, but fallback = 0
+    if (pq.how[c] != SR_EXPLAIN_NONE) continue;
+    out->feasible[c] = out->first[c] = -1;
+    std::fill_n(out->counts + static_cast<size_t>(c) * SR_WHY_COUNT, SR_WHY_COUNT, 0);
+    if (out->node_mask) std::fill_n(out->node_mask + c * ns, ns, uint16_t(0));
+    if (out->fallback) out->fallback[c] = 0;
+  }
+  const int32_t nb = static_cast<int32_t>(pq.batched.size());
+  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data());
+  if (st != SR_OK) return st;
+  if (nb > 1)
+    for (int32_t i = 0; i < nb; ++i)
+      if (ctx->x_wl.status_host[i] == SR_CAND_FALLBACK) pq.how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
+  const int32_t* off = cands->cand_pod_off;
+  for (int32_t c = 0; c < nc; ++c) {
+    if (pq.how[c] != SR_EXPLAIN_SINGLE) continue;
+    st = sr_snapshot_fork(snap);
+    if (st != SR_OK) return st;
+    const int32_t* pods = cands->cand_pods + off[c];
+    // (node_of_pod may be NULL when no asked candidate has an earlier pod)
+    const int32_t* map = node_of_pod ? node_of_pod + (off[c] - off[0]) : nullptr;
+    for (int32_t k = 0; k < at_pod[c]; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], map[k]);
+    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c);
+    const sr_status rv = sr_snapshot_revert(snap);
+    if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
+  }
+  if (out_how) std::copy(pq.how.begin(), pq.how.end(), out_how);
+  return SR_OK;
 }
 
 sr_status sr_set_timing(sr_ctx* ctx, int32_t mask) {

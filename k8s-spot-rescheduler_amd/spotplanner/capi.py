@@ -405,6 +405,9 @@ def _declare_planner(lib):
     lib.sr_explain_candidate.argtypes = [VP, VP, PC, P32, ctypes.c_int32, P32, ctypes.c_int32,
                                          ctypes.POINTER(sr_explain_out)]
     lib.sr_explain_candidate.restype = S
+    lib.sr_explain_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32, ctypes.POINTER(sr_explain_out),
+                                    PU8]
+    lib.sr_explain_plan.restype = S
     lib.sr_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
     lib.sr_plan.restype = S
     lib.sr_plan_first.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
@@ -440,7 +443,7 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_add_pod", "sr_snapshot_fork", "sr_snapshot_revert", "sr_snapshot_node_state",
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
             "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_explain_pods", "sr_explain_candidate",
-            "sr_plan", "sr_plan_first", "sr_plan_sequence",
+            "sr_explain_plan", "sr_plan", "sr_plan_first", "sr_plan_sequence",
             "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",
             "sr_comm_init_shm"]

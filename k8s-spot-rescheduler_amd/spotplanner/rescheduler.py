@@ -6,7 +6,9 @@ segment of run() (:228-287) evaluated for every candidate at once on the GPU.
 plan_sequence_arrays / drainSequence go beyond the reference, which drains one
 node per tick: several consistent drains planned in one tick (sr_plan_sequence).
 explainPods / explainCandidate batch the per-node log line of :348: which filter
-groups refuse a pod on each spot node (sr_explain_pods).
+groups refuse a pod on each spot node (sr_explain_pods); explainPlan does it for
+every stuck candidate of a plan at once, each stop pod judged after the
+candidate's own earlier pods (sr_explain_plan).
 """
 from __future__ import annotations
 
@@ -312,6 +314,7 @@ class ExplainResult:
     fallback: np.ndarray             # [n] 1: outside the encoded predicate set, nothing evaluated
     node_mask: Optional[np.ndarray]  # [n][n_spot] the mask of every node (None: not asked for)
     n_spot: int = 0
+    how: Optional[np.ndarray] = None  # explain_plan_arrays: [n] capi.SR_EXPLAIN_* the way each candidate went
 
     def reasons(self, i: int = 0) -> dict:
         """{reason name: nodes refusing for it} of pod i, reasons no node gives left out."""
@@ -387,3 +390,45 @@ def explainCandidate(predicateChecker: PredicateChecker, spotSnapshot: ClusterSn
     node_of_pod = np.array([pos.get(mapping[k], -1) if k < at_pod else -1 for k in range(len(pods))], np.int32)
     return explain_candidate_arrays(predicateChecker, spotSnapshot.handle, enc.ptr,
                                     np.arange(len(pods), dtype=np.int32), node_of_pod, at_pod, node_mask)
+
+
+def explain_plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
+                        cand_pods: np.ndarray, at_pod: np.ndarray, node_of_pod: np.ndarray,
+                        node_mask: bool = True) -> ExplainResult:
+    """sr_explain_plan: candidate c's pod at_pod[c] (negative: not asked; plan.status as it is) explained with its
+    earlier pods at node_of_pod (plan.node_of_pod; None is allowed when no asked candidate has an earlier pod);
+    results by candidate, `how` says which way each went."""
+    lib = predicateChecker.lib
+    cand_off = np.ascontiguousarray(cand_off, np.int32)
+    cand_pods = np.ascontiguousarray(cand_pods, np.int32)
+    at_pod = np.ascontiguousarray(at_pod, np.int32)
+    if node_of_pod is not None:
+        node_of_pod = np.ascontiguousarray(node_of_pod, np.int32)
+    n = len(cand_off) - 1
+    if len(at_pod) != n:
+        raise ValueError("at_pod needs one entry per candidate")
+    c = capi.sr_candidates(n, capi.ptr(cand_off, capi.P32), capi.ptr(cand_pods, capi.P32), None)
+    o, res = _explain_out(n, lib.sr_snapshot_num_nodes(snapshot_handle), node_mask)
+    how = np.zeros(max(n, 1), np.uint8)
+    st = lib.sr_explain_plan(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                             capi.ptr(at_pod, capi.P32),
+                             capi.ptr(node_of_pod, capi.P32) if node_of_pod is not None else None, ctypes.byref(o),
+                             capi.ptr(how, capi.PU8))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_explain_plan: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    res.how = how[:n]
+    return res
+
+
+def explainPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                candidates: Sequence[Sequence[Pod]], plan, node_mask: bool = True) -> ExplainResult:
+    """Why every stuck candidate of `plan` (plan_arrays' result for `candidates`) stopped, in one call."""
+    _check_order(spotSnapshot, nodes)
+    flat = [p for c in candidates for p in c]
+    enc = spotSnapshot.encode_pods(flat)
+    cand_off = np.zeros(len(candidates) + 1, np.int32)
+    cand_off[1:] = np.cumsum([len(c) for c in candidates])
+    return explain_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
+                               np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod, node_mask)

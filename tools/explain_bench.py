@@ -11,7 +11,18 @@ oracle_check_predicates over the same (pod, node) pairs on one thread; its
 time includes one binding call per pair.  Every mask is checked against the
 oracle's answer (mask == 0 iff yes).  One JSON line per config.
 
-  python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE]
+--plan times sr_explain_plan instead: after the tick's plan, host to host on
+one box in one call, (a) one explain_plan_arrays call over the tick's status,
+(b) the loop of explain_candidate_arrays over the same failing candidates,
+which is what answers the question exactly without the batched entry point,
+and (c) the sr_explain_pods call above, which answers it against the base
+snapshot.  Each the median of --reps after two warm-up calls.  It reports the
+failing candidates, how many stop at a pod k > 0, how many went each way
+(`how`), and how many stop pods look feasible against the base snapshot but are
+not in context; mask == 0 is checked against the oracle forked and filled the
+same way, and (a) against (b) field for field.
+
+  python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan]
 """
 import argparse
 import json
@@ -29,7 +40,8 @@ from oracle_lib import load_oracle  # noqa: E402
 from sequence_ref import from_synth  # noqa: E402
 from spotplanner import capi  # noqa: E402
 from spotplanner.planner import PredicateChecker  # noqa: E402
-from spotplanner.rescheduler import explain_arrays, plan_arrays  # noqa: E402
+from spotplanner.rescheduler import (explain_arrays, explain_candidate_arrays, explain_plan_arrays,  # noqa: E402
+                                     plan_arrays)
 from spotplanner.synth import SynthCluster  # noqa: E402
 
 
@@ -39,16 +51,98 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, r
 
 
+def median_of(fn, reps):
+    for _ in range(2):
+        fn()
+    ms = [timed(fn)[0] for _ in range(reps)]
+    return round(statistics.median(ms), 3), round(min(ms), 3), round(max(ms), 3)
+
+
+def plan_mode(args, ck, lib, config):
+    inp = from_synth(SynthCluster(config))
+    h = inp.product_snapshot()
+    n_spot = len(inp.spot)
+    off, cp = inp.cand_off, inp.cand_pods
+    rel = off - off[0]  # node_of_pod is relative to cand_pod_off[0]
+    try:
+        plan = plan_arrays(ck, h, inp.ptr, off, cp)
+        status, mapping = np.array(plan.status, np.int32), np.array(plan.node_of_pod, np.int32)
+        failing = [c for c in range(len(status)) if status[c] >= 0]
+        stops = np.array([cp[off[c] + status[c]] for c in failing], np.int32)
+
+        def batched(mask=True):
+            return explain_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping, node_mask=mask)
+
+        def loop(mask=True):
+            return [explain_candidate_arrays(ck, h, inp.ptr, cp[off[c]:off[c + 1]], mapping[rel[c]:rel[c + 1]],
+                                             int(status[c]), node_mask=mask) for c in failing]
+        res, singles = batched(), loop()
+        same = all(res.fallback[c] == one.fallback[0] and res.feasible[c] == one.feasible[0] and
+                   res.first[c] == one.first[0] and np.array_equal(res.counts[c], one.counts[0]) and
+                   np.array_equal(res.node_mask[c], one.node_mask[0]) for c, one in zip(failing, singles))
+        base = explain_arrays(ck, h, inp.ptr, stops, node_mask=False)
+        line = dict(config=config, mode="plan", n_cand=len(status), n_failing=len(failing), n_spot=n_spot,
+                    failing_at_later_pod=int(np.sum(status > 0)),
+                    how={name: int(np.sum(res.how == v)) for name, v in
+                         (("none", capi.SR_EXPLAIN_NONE), ("batched", capi.SR_EXPLAIN_BATCHED),
+                          ("single", capi.SR_EXPLAIN_SINGLE))},
+                    fallback_stop_pods=int(res.fallback.sum()),
+                    feasible_on_base_not_in_context=int(sum(
+                        1 for i, c in enumerate(failing) if base.feasible[i] > 0 and res.feasible[c] == 0)),
+                    batched_equals_loop=bool(same), reps=args.reps)
+        print("# timing the batched call", file=sys.stderr, flush=True)
+        for name, mask in (("with_node_mask", True), ("counts_only", False)):
+            m = median_of(lambda: batched(mask), args.reps)
+            line.update({"ms_explain_plan_%s_median" % name: m[0], "ms_explain_plan_%s_min" % name: m[1],
+                         "ms_explain_plan_%s_max" % name: m[2]})
+        print("# timing the per-candidate loop", file=sys.stderr, flush=True)
+        m = median_of(loop, args.reps)
+        line.update(ms_candidate_loop_median=m[0], ms_candidate_loop_min=m[1], ms_candidate_loop_max=m[2])
+        m = median_of(lambda: explain_arrays(ck, h, inp.ptr, stops), args.reps)
+        line.update(ms_explain_pods_base_median=m[0], ms_explain_pods_base_min=m[1], ms_explain_pods_base_max=m[2])
+        if line["ms_explain_plan_with_node_mask_median"] > 0:
+            line["ratio_loop_over_explain_plan"] = round(
+                line["ms_candidate_loop_median"] / line["ms_explain_plan_with_node_mask_median"], 1)
+    finally:
+        lib.sr_snapshot_destroy(h)
+    if not args.no_oracle and len(failing):
+        print("# checking against the oracle", file=sys.stderr, flush=True)
+        ora = load_oracle()
+        osnap = inp.oracle_snapshot()
+        ok = True
+        for c in failing:
+            if res.fallback[c]:
+                continue
+            assert ora.oracle_snapshot_fork(osnap.h) == 0
+            for k in range(int(status[c])):
+                ora.oracle_snapshot_add_pod(osnap.h, inp.ptr, int(cp[off[c] + k]), int(mapping[rel[c] + k]))
+            pod = int(cp[off[c] + status[c]])
+            fits = np.array([ora.oracle_check_predicates(osnap.h, inp.ptr, pod, j) for j in range(n_spot)], np.int32)
+            ora.oracle_snapshot_revert(osnap.h)
+            ok = ok and bool(np.array_equal(res.node_mask[c] == 0, fits == 1))
+        osnap.close()
+        line["matches_oracle_in_context"] = ok
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="3")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--no-oracle", action="store_true")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    ap.add_argument("--plan", action="store_true", help="time sr_explain_plan against the per-candidate loop")
     args = ap.parse_args()
     ck = PredicateChecker(0)
     lib = capi.load_planner()
     for config in [int(x) for x in args.configs.split(",")]:
+        if args.plan:
+            text = json.dumps(plan_mode(args, ck, lib, config))
+            print(text, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(text + "\n")
+            continue
         inp = from_synth(SynthCluster(config))
         h = inp.product_snapshot()
         try:

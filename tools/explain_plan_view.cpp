@@ -1,0 +1,100 @@
+// Host-only view of sr_explain_plan's batched pass (csrc/explain_plan.cpp):
+// built to lib/libsrexplainview.so together with the HIP-free encoder objects,
+// so tests/test_explain_plan_reference.py can prove everything but the kernel
+// without a GPU: which way every asked candidate goes, the context lists and
+// the nodes' pod slack as the kernel reads them, and every batched query's
+// per-node masks, evaluated by explain_node_ctx -- the statement the kernel
+// follows.  Not part of libsrplanner.so or the ABI: the library carries its
+// own copy of sr_snapshot_create / sr_snapshot_add_pod / sr_snapshot_destroy,
+// and the snapshot passed in must come from it.
+//   make -C k8s-spot-rescheduler_amd tools
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../k8s-spot-rescheduler_amd/csrc/explain_plan.hpp"
+#include "../k8s-spot-rescheduler_amd/csrc/host.hpp"
+
+extern "C" {
+
+// how[n_cand]; ctx_off[n_cand + 1] into ctx_node / ctx_pods / ctx_acc[.][3]
+// (cap_entries entries each; a candidate that is not batched has an empty
+// list); node_slack[n_spot]; atom0[n_spot] the encode's atom-0 row, bit by bit
+// (255 everywhere when nothing is batched: no encode); node_mask[n_cand][n_spot]
+// and fallback[n_cand] for the batched candidates (others: zeros).  As in the
+// planner, a stop pod the batched encode hands back as fallback while other
+// pods were in the batch goes the SINGLE way (the view does not evaluate it:
+// zeros); alone in its batch it stays BATCHED with fallback = 1.
+sr_status sr_explain_plan_view(const sr_cluster* cluster, const sr_snapshot* snap, const sr_candidates* cands,
+                               const int32_t* at_pod, const int32_t* node_of_pod, uint8_t* how, int32_t* ctx_off,
+                               int32_t* ctx_node, int32_t* ctx_pods, int64_t* ctx_acc, int32_t cap_entries,
+                               int32_t* node_slack, uint8_t* atom0, uint16_t* node_mask, uint8_t* fallback) {
+  if (!cluster || !snap || !cands || !at_pod || !how || !ctx_off || !node_slack || !atom0 || !node_mask || !fallback)
+    return SR_ERR_INVALID_ARG;
+  sr::PlanQueries pq;
+  sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
+  if (st != SR_OK) return st;
+  const int32_t nc = cands->n_cand, nb = static_cast<int32_t>(pq.batched.size());
+  const size_t ns = snap->nodes.size();
+  if (static_cast<int32_t>(pq.entries.size()) > cap_entries) return SR_ERR_INVALID_ARG;
+  std::copy(pq.how.begin(), pq.how.end(), how);
+  std::fill_n(node_mask, static_cast<size_t>(nc) * ns, uint16_t(0));
+  std::fill_n(fallback, nc, uint8_t(0));
+  std::fill_n(atom0, ns, uint8_t(255));
+  ctx_off[0] = 0;
+  for (int32_t c = 0, b = 0; c < nc; ++c) {
+    ctx_off[c + 1] = ctx_off[c];
+    if (b < nb && pq.batched[b] == c) {
+      for (int32_t j = pq.off[b]; j < pq.off[b + 1]; ++j) {
+        const int32_t o = ctx_off[c + 1]++;
+        ctx_node[o] = pq.entries[j].node;
+        ctx_pods[o] = pq.entries[j].pods;
+        for (int d = 0; d < 3; ++d) ctx_acc[o * 3 + d] = pq.entries[j].acc[d];
+      }
+      ++b;
+    }
+  }
+  if (nb == 0) {
+    std::vector<int32_t> slack;
+    sr::node_slack(snap, static_cast<int32_t>(ns), &slack);
+    std::copy(slack.begin(), slack.end(), node_slack);
+    return SR_OK;
+  }
+  // the stop pods as candidates of their own against the base snapshot, tags on
+  std::vector<int32_t> off(static_cast<size_t>(nb) + 1);
+  for (int32_t i = 0; i <= nb; ++i) off[i] = i;
+  const sr_candidates stops{nb, off.data(), pq.pods.data(), nullptr};
+  sr::EncoderCache cache;
+  cache.want_why = true;
+  sr::Workload w;
+  std::string err;
+  st = sr::encode_workload(&cache, snap, cluster, &stops, &w, &err);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < nb; ++i) {
+    if (w.status_host[i] != SR_CAND_FALLBACK) continue;
+    if (nb > 1) how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
+    else fallback[pq.batched[i]] = 1;
+  }
+  std::vector<int32_t> slack;
+  sr::node_slack(snap, std::max(w.n_pad, static_cast<int32_t>(ns)), &slack);
+  std::copy_n(slack.begin(), ns, node_slack);
+  if (w.n_atoms > 0 && w.atoms.size() >= static_cast<size_t>(w.Wp) && static_cast<size_t>(w.Wp) * 64 >= ns)
+    for (size_t j = 0; j < ns; ++j) atom0[j] = static_cast<uint8_t>(w.atoms[j >> 6] >> (j & 63) & 1);
+  const int32_t na = static_cast<int32_t>(w.pod_src.size());
+  if (na == 0) return SR_OK;
+  sr::ExplainPrograms x;
+  std::vector<sr::ExplainPod> xp;
+  if (!sr::build_explain(w, &x) || w.pod_cls.size() != static_cast<size_t>(na)) return SR_ERR_STATE;
+  sr::explain_pods(w, &xp);
+  for (int32_t q = 0; q < na; ++q) {
+    const int32_t i = w.pod_src[q] - w.pod_base;
+    const sr::PlanCtxEntry *lo = pq.entries.data() + pq.off[i], *hi = pq.entries.data() + pq.off[i + 1];
+    uint16_t* row = node_mask + static_cast<size_t>(pq.batched[i]) * ns;
+    for (int32_t node = 0; node < static_cast<int32_t>(ns); ++node)
+      row[node] = static_cast<uint16_t>(sr::explain_node_ctx(x, xp[q], w.atoms.data(), w.Wp, cache.node_free.data(),
+                                                             w.n_pad, node, slack[node], sr::find_ctx(lo, hi, node)));
+  }
+  return SR_OK;
+}
+
+}  // extern "C"
