@@ -20,7 +20,11 @@ to queries with empty lists.
 
 tests/test_explain_plan_reference.py proves the cases on the CPU (the view
 library and the oracle), tests/test_gpu_explain_plan.py runs them through the
-C ABI."""
+C ABI.  Past these sizes -- pools of 320 to 4,300 nodes, lists of thousands of
+entries, 300 classes, the second launch of the grid split, the quantity limit
+of the plain rule -- tests/explain_plan_sizes.py takes over, with
+tests/test_explain_plan_sizes_reference.py and
+tests/test_gpu_explain_plan_sizes.py."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

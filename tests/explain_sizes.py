@@ -226,9 +226,12 @@ class Pool:
     variants: Dict[int, int]
     firsts: List[int]
     many: List[int] = field(default_factory=list)
+    extra: List[int] = field(default_factory=list)
 
 
-def build(n: int, roomy: bool = False, many: bool = False, variants: bool = True) -> Pool:
+def build(n: int, roomy: bool = False, many: bool = False, variants: bool = True, extra=()) -> Pool:
+    """`extra`: further query pods, after all others (explain_plan_sizes.py: the pods of its candidates); the
+    nodes, the base pods and the indices of every other query pod come out as without them."""
     nodes, base = [], []
     for j in range(n):
         labels = {H: "s%d" % j, "a": "a%d" % (j % 4), "b": "b%d" % (j % 5)}
@@ -279,10 +282,13 @@ def build(n: int, roomy: bool = False, many: bool = False, variants: bool = True
     m0 = len(query)
     if many:
         query += [many_pod(i) for i in range(MANY)]
+    x0 = len(query)
+    query += list(extra)
     sc = Scenario(nodes, base, query, volumes=VolumeWorld())
     return Pool(n, sc, sc.qidx(0), {bit: sc.qidx(q) for bit, q in vq.items()},
                 [sc.qidx(f0 + s) for s in range(len(FIRST_SETS))],
-                [sc.qidx(m0 + i) for i in range(MANY)] if many else [])
+                [sc.qidx(m0 + i) for i in range(MANY)] if many else [],
+                [sc.qidx(x0 + i) for i in range(len(extra))])
 
 
 @lru_cache(maxsize=None)
