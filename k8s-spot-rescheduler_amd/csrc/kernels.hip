@@ -504,6 +504,8 @@ struct K2Lds {
   int32_t omap[kMaxPods];           // spot position chosen for each pod
 };
 
+constexpr int kMapG = 4;  // node order: pod groups of 64 (<= 256 pods), one mapping register per lane and group
+
 struct K2Stats {
   uint32_t n_spec_miss = 0, n_min = 0, n_far = 0;
   uint64_t cyc_a = 0, cyc_b = 0, cyc_c = 0, cyc_d = 0;
@@ -512,6 +514,9 @@ struct K2Stats {
   uint64_t cyc_res = 0;  // node order: far-pointer resolution cycles (part of cyc_b) | chunk rounds << 40 | pods
                          // found dead << 56
   uint64_t cyc_win = 0;  // node order: window record loads waited for (part of cyc_b)
+  // node order (profile builds): of the prologue (cyc_a) and of the far resolutions (cyc_res), the cycles from a
+  // batch's first load to its last one's return -- the rest consumes them; the resolutions and their pending pods
+  uint32_t cyc_a_ld = 0, cyc_res_ld = 0, n_res = 0, n_res_pods = 0;
 };
 
 // One candidate's canDrainNode with 64 * SPL touched-node slots.  Returns the
@@ -1440,9 +1445,10 @@ __device__ __forceinline__ int wave_sum(int v) {
 template <int G, bool PROF, bool WIDE = false, bool XT = false, bool COOP = false>
 __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __restrict__ F, const int p0,
                                               const int np, int& status, K2Stats& st, uint32_t& nbytes,
-                                              const int ebase = -1, const int erow0_in = -2,
+                                              int (&mapv)[kMapG], const int ebase = -1, const int erow0_in = -2,
                                               const int erow1_in = -2, CoopArea* A = nullptr) {
   static_assert(64 * G * kNHS * 8 <= sizeof(K2Lds), "node-order LDS exceeds the wave's K2 region");
+  static_assert(G <= kMapG, "a mapping register per pod group");
   const int lane = threadIdx.x & 63;
   const int Wp = w.Wp;
   const uint64_t* __restrict__ tab = w.S;
@@ -1673,6 +1679,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
         uint64_t x[kPB][4];
         int kk[kPB];
         uint32_t fm[kPB];  // the pod's fit mask of the changed nodes (K0-less runs), with its row offsets
+        const uint64_t cyc_ld0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
 #pragma unroll
         for (int h = 0; h < kPB; ++h) {
           kk[h] = b0 + kPW * h + sub;
@@ -1690,6 +1697,10 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
           x[h][1] = tab[o1 + wi];
           x[h][2] = tab[o2 + wi];
           x[h][3] = tab[o3 + wi];
+        }
+        if (PROF) {  // profile builds: the batch's rows waited for here
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          st.cyc_a_ld += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - cyc_ld0);
         }
 #pragma unroll
         for (int h = 0; h < kPB; ++h) {
@@ -1760,10 +1771,15 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
     uint64_t unres_n = 0;
     if (n == kFar || (n & 4095) == 0) {  // wave-uniform
 #pragma unroll
-      for (int g = 0; g < G; ++g) unres_n |= ballot(((act[g] >> lane) & 1) && ptr[g] == n && unres[g]);
+      for (int g = 0; g < G; ++g) {
+        const uint64_t u = ballot(((act[g] >> lane) & 1) && ptr[g] == n && unres[g]);
+        unres_n |= u;
+        if (PROF) st.n_res_pods += static_cast<uint32_t>(__builtin_popcountll(u));
+      }
     }
     if (unres_n != 0) {
       const uint64_t cyc_r0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
+      if (PROF) st.n_res += 1;
       const int sw = n >> 6;  // first word to scan (every pending pod points at n)
       // Q pods per round, all their loads for one chunk in flight together:
       // 4 row words each, or (s_head_only) their programs' atom words and 3 T
@@ -1808,6 +1824,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
               const uint32_t wi = wv ? static_cast<uint32_t>(word) : 0u;
               if (PROF) st.cyc_res += 1ull << 40;  // chunk rounds
               uint64_t x[Q][HO ? 11 : 4];
+              const uint64_t cyc_ld0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
 #pragma unroll
               for (int q = 0; q < Q; ++q) {
                 if (!((todo >> q) & 1)) continue;  // wave-uniform
@@ -1824,6 +1841,10 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
                   x[q][2] = tab[static_cast<uint32_t>(a23[q]) + wi];
                   x[q][3] = tab[static_cast<uint32_t>(a23[q] >> 32) + wi];
                 }
+              }
+              if (PROF) {  // profile builds: the round's words waited for here
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                st.cyc_res_ld += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - cyc_ld0);
               }
               const uint64_t vw = ballot(wv);
 #pragma unroll
@@ -2119,7 +2140,8 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int k = 64 * g + lane;
-    if (k < np) w.out_node[p0 + k] = k < dead ? node[g] : -1;
+    mapv[g] = k < dead ? node[g] : -1;  // (k2_finish: the winner's mapping without a read-back)
+    if (k < np) w.out_node[p0 + k] = mapv[g];
   }
 }
 
@@ -2575,9 +2597,13 @@ __device__ __forceinline__ void k2_skipped(const DevWorkload& w, int ci) {
   if (w.out_cycles) w.out_cycles[ci] = 0;
 }
 
+// The candidate's mapping, where the wave still holds it: `mapv` when in_regs
+// (node order: pod 64 * g + lane in mapv[g]) or `lmap` (pod order: the wave's
+// L.omap).  The domain path hands over neither.
 template <bool PROF>
 __device__ __forceinline__ void k2_finish(const DevWorkload& w, const K2Entry& x, int status, int wide,
-                                          uint32_t nbytes, const K2Stats& st) {
+                                          uint32_t nbytes, const K2Stats& st, const int (&mapv)[kMapG],
+                                          const bool in_regs = true, const int32_t* lmap = nullptr) {
   const int lane = threadIdx.x & 63;
   const int ci = x.ci, p0 = x.p0, np = x.np;
   int best = 0;  // lane 0: this candidate is the first drainable one so far
@@ -2606,11 +2632,14 @@ __device__ __forceinline__ void k2_finish(const DevWorkload& w, const K2Entry& x
       pr[9] = st.cyc_b;
       pr[10] = st.cyc_c;
       pr[11] = st.cyc_d;
-      if (wide == 2) {  // node order
+      if (wide == 2) {  // node order (sections of a wave stay far below 2^32 cycles: the high halves carry the split)
+        pr[8] |= static_cast<uint64_t>(st.cyc_a_ld) << 32;
+        pr[10] |= static_cast<uint64_t>(st.n_res_pods) << 32 | static_cast<uint64_t>(st.n_res) << 48;
+        pr[11] |= static_cast<uint64_t>(st.cyc_res_ld) << 32;
         pr[12] = st.cyc_res;
         pr[13] = st.cyc_win;
         pr[14] = st.cyc_rec - x.c_start;
-        pr[15] = st.narrow;
+        pr[15] = st.narrow | (status < 0 ? 16u : 0u);  // (16: the candidate is drainable)
       }
     }
   }
@@ -2623,12 +2652,28 @@ __device__ __forceinline__ void k2_finish(const DevWorkload& w, const K2Entry& x
     // and is accepted on its own: no store waits for another.
     const uint64_t tag = static_cast<uint64_t>(w.seq) << 32;
     if (__builtin_amdgcn_readfirstlane(best)) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's out_node stores, then read back
-      for (int q = lane; q < np; q += 64)
-        __hip_atomic_store(w.res_map + p0 + q,
-                           tag | static_cast<uint32_t>(__hip_atomic_load(w.out_node + p0 + q, __ATOMIC_RELAXED,
-                                                                         __HIP_MEMORY_SCOPE_AGENT)),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      // a first drainable candidate placed every pod: the mapping is whole in
+      // the wave's registers or LDS, and goes out without waiting for the
+      // out_node stores (SR_K2_MAP_REGS=0: read back from out_node, as the
+      // domain path does)
+      if (in_regs && w.k2_map_regs) {
+#pragma unroll
+        for (int g = 0; g < kMapG; ++g)
+          if (64 * g + lane < np)
+            __hip_atomic_store(w.res_map + p0 + 64 * g + lane, tag | static_cast<uint32_t>(mapv[g]), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+      } else if (lmap && w.k2_map_regs) {
+        for (int q = lane; q < np; q += 64)
+          __hip_atomic_store(w.res_map + p0 + q, tag | static_cast<uint32_t>(lmap[q]), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+      } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's out_node stores, then read back
+        for (int q = lane; q < np; q += 64)
+          __hip_atomic_store(w.res_map + p0 + q,
+                             tag | static_cast<uint32_t>(__hip_atomic_load(w.out_node + p0 + q, __ATOMIC_RELAXED,
+                                                                           __HIP_MEMORY_SCOPE_AGENT)),
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
     }
     if (lane == 0)
       __hip_atomic_store(w.res_stat + ci, tag | (status < 0 ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2656,6 +2701,8 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   int status = -1;
   int wide = 0;
   uint32_t nbytes = 0;
+  int mapv[kMapG] = {-1, -1, -1, -1};
+  bool in_regs = false, in_lds = false;  // where the mapping is at hand for k2_finish
   const int dbase = w.dyn_cand ? __builtin_amdgcn_readfirstlane(w.dyn_cand[ci]) : -1;
   const int ebase = w.ext_cand ? __builtin_amdgcn_readfirstlane(w.ext_cand[ci]) : -1;
   const bool node_order = np <= 4 * 64 && w.k2_mode == 0;
@@ -2669,27 +2716,31 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   } else if (node_order && ebase >= 0) {  // extension records, node order (place_window_x); writes out_node
     uint64_t* F = reinterpret_cast<uint64_t*>(&L);
     wide = 2;
-    if (np <= 64) k2_node_order<1, PROF, false, true>(w, F, p0, np, status, st, nbytes, ebase);
-    else if (np <= 128) k2_node_order<2, PROF, false, true>(w, F, p0, np, status, st, nbytes, ebase);
-    else k2_node_order<4, PROF, false, true>(w, F, p0, np, status, st, nbytes, ebase);
+    if (np <= 64) k2_node_order<1, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
+    else if (np <= 128) k2_node_order<2, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
+    else k2_node_order<4, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
+    in_regs = true;
   } else if (ebase >= 0) {  // extension records, pod order (SR_K2_MODE=1) with the extended running state
     int placed = k2_run<1, CH, PROF, true>(w, L, p0, np, status, st, nbytes, ebase);
     wide = placed < 0 ? 1 : 0;
     if (placed < 0) placed = k2_run<8, CH, PROF, true>(w, L, p0, np, status, st, nbytes, ebase);
     for (int i = lane; i < np; i += 64) w.out_node[p0 + i] = i < placed ? L.omap[i] : -1;
+    in_lds = true;
   } else if (node_order) {  // writes out_node itself
     uint64_t* F = reinterpret_cast<uint64_t*>(&L);
     wide = 2;
-    if (np <= 64) k2_node_order<1, PROF>(w, F, p0, np, status, st, nbytes);
-    else if (np <= 128) k2_node_order<2, PROF>(w, F, p0, np, status, st, nbytes);
-    else k2_node_order<4, PROF>(w, F, p0, np, status, st, nbytes);
+    if (np <= 64) k2_node_order<1, PROF>(w, F, p0, np, status, st, nbytes, mapv);
+    else if (np <= 128) k2_node_order<2, PROF>(w, F, p0, np, status, st, nbytes, mapv);
+    else k2_node_order<4, PROF>(w, F, p0, np, status, st, nbytes, mapv);
+    in_regs = true;
   } else {
     int placed = k2_run<1, CH, PROF>(w, L, p0, np, status, st, nbytes);
     wide = placed < 0 ? 1 : 0;
     if (placed < 0) placed = k2_run<8, CH, PROF>(w, L, p0, np, status, st, nbytes);  // > 64 distinct nodes
     for (int i = lane; i < np; i += 64) w.out_node[p0 + i] = i < placed ? L.omap[i] : -1;
+    in_lds = true;
   }
-  k2_finish<PROF>(w, x, status, wide, nbytes, st);
+  k2_finish<PROF>(w, x, status, wide, nbytes, st, mapv, in_regs, in_lds ? L.omap : nullptr);
 }
 
 // K2 when every candidate of the launch takes node order (no domain-path
@@ -2736,16 +2787,17 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
       K2Stats st;
       int status = -1;
       uint32_t nbytes = 0;
+      int mapv[kMapG] = {-1, -1, -1, -1};
       if (GMAX == 1 || x.np <= 64)
-        k2_node_order<1, PROF, false, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, -1, -2, -2, A);
+        k2_node_order<1, PROF, false, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, mapv, -1, -2, -2, A);
       else if (GMAX == 2 || x.np <= 128)
-        k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, -1,
+        k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, mapv, -1,
                                                                     -2, -2, A);
-      else k2_node_order<GMAX, PROF, WIDE, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, -1, -2, -2, A);
+      else k2_node_order<GMAX, PROF, WIDE, false, true>(w, k2_lds, x.p0, x.np, status, st, nbytes, mapv, -1, -2, -2, A);
       if (threadIdx.x == 0) A->cmd = 1;  // the helpers leave
       __syncthreads();
       st.narrow |= 2;  // (profile: a cooperative block)
-      k2_finish<PROF>(w, x, status, 2, nbytes, st);
+      k2_finish<PROF>(w, x, status, 2, nbytes, st, mapv);
       return;
     }
   }
@@ -2762,24 +2814,25 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
   K2Stats st;
   int status = -1;
   uint32_t nbytes = 0;
+  int mapv[kMapG] = {-1, -1, -1, -1};
   if constexpr (XT) {
     const int ebase = __builtin_amdgcn_readfirstlane(xe.x);
     const int er0 = __builtin_amdgcn_readfirstlane(xe.y), er1 = __builtin_amdgcn_readfirstlane(xe.z);
     if (ebase >= 0) {
       if (GMAX == 1 || x.np <= 64)
-        k2_node_order<1, PROF, false, true>(w, F, x.p0, x.np, status, st, nbytes, ebase, er0, er1);
+        k2_node_order<1, PROF, false, true>(w, F, x.p0, x.np, status, st, nbytes, mapv, ebase, er0, er1);
       else if (GMAX == 2 || x.np <= 128)
-        k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE, true>(w, F, x.p0, x.np, status, st, nbytes, ebase, er0, er1);
-      else k2_node_order<GMAX, PROF, WIDE, true>(w, F, x.p0, x.np, status, st, nbytes, ebase, er0, er1);
-      k2_finish<PROF>(w, x, status, 2, nbytes, st);
+        k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE, true>(w, F, x.p0, x.np, status, st, nbytes, mapv, ebase, er0, er1);
+      else k2_node_order<GMAX, PROF, WIDE, true>(w, F, x.p0, x.np, status, st, nbytes, mapv, ebase, er0, er1);
+      k2_finish<PROF>(w, x, status, 2, nbytes, st, mapv);
       return;
     }
   }
-  if (GMAX == 1 || x.np <= 64) k2_node_order<1, PROF>(w, F, x.p0, x.np, status, st, nbytes);
+  if (GMAX == 1 || x.np <= 64) k2_node_order<1, PROF>(w, F, x.p0, x.np, status, st, nbytes, mapv);
   else if (GMAX == 2 || x.np <= 128)
-    k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE>(w, F, x.p0, x.np, status, st, nbytes);
-  else k2_node_order<GMAX, PROF, WIDE>(w, F, x.p0, x.np, status, st, nbytes);
-  k2_finish<PROF>(w, x, status, 2, nbytes, st);
+    k2_node_order<(GMAX >= 2 ? 2 : 1), PROF, WIDE>(w, F, x.p0, x.np, status, st, nbytes, mapv);
+  else k2_node_order<GMAX, PROF, WIDE>(w, F, x.p0, x.np, status, st, nbytes, mapv);
+  k2_finish<PROF>(w, x, status, 2, nbytes, st, mapv);
 }
 
 // Launch with optional HIP events recorded by the dispatch itself

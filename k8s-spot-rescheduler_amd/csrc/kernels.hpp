@@ -116,6 +116,8 @@ struct DevWorkload {
   int32_t k2_narrow;   // node order: 32-bit scaled window visits where every request allows (SR_K2_NARROW=0: never)
   int32_t k2_wpb;      // K2 waves per block (SR_K2_WPB: 1, 2 or 4; 0 = 1 up to 2,048 entries, else 4)
   int32_t k2_excl;     // node order: exclusive candidates placed with the taken-mask step (SR_K2_EXCL=0: never)
+  int32_t k2_map_regs; // the first drainable candidate's res_map words come from the wave's registers (node order) or
+                       // LDS (pod order) instead of a fence and a read of out_node (SR_K2_MAP_REGS=0: never)
   int32_t n_coop;      // node-order kernel, four waves per block: the first n_coop work-list entries (the costliest)
                        // are planned by one block each, its other waves scanning far resolutions with the chain
   int32_t cand_floor;  // sr_plan_sequence rounds: a K2 wave whose entry's global index is <= cand_floor plans

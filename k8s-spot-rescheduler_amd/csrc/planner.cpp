@@ -195,6 +195,7 @@ struct sr_ctx {
   int32_t k2_narrow = 1;      // SR_K2_NARROW: 32-bit scaled window visits in node order (0: 64-bit only)
   int32_t k2_wpb = 0;         // SR_K2_WPB: K2 waves per block (1, 2, 4; 0 = by list length)
   int32_t k2_excl = 1;        // SR_K2_EXCL: exclusive candidates (one host port) with the taken-mask step
+  int32_t k2_map_regs = 1;    // SR_K2_MAP_REGS: the winner's mapping goes to the host from the wave's registers / LDS
   int32_t k2_node_kernel = 1; // SR_K2_NODE_KERNEL: node-order-only K2 kernel when every candidate takes that path
   int32_t s_head_only = 1;    // SR_S_HEAD_ONLY: K0 writes S-row heads only on rows wider than 64 words (0: never)
   // sr_explain_pods: an encoder, a workload and buffers of its own, outside the slots, the workload arenas and
@@ -641,6 +642,7 @@ sr_status fill_dev_workload(sr_ctx* ctx, Slot& sl) {
   d.k2_narrow = ctx->k2_narrow;
   d.k2_wpb = ctx->k2_wpb;
   d.k2_excl = ctx->k2_excl;
+  d.k2_map_regs = ctx->k2_map_regs;
   d.k2_node_kernel = ctx->k2_node_kernel;
   // Wide rows, every candidate on the node-order kernel and every class
   // program in its 8-slot record: K0 writes only the S-row heads, K2
@@ -1410,6 +1412,7 @@ sr_status sr_create(int32_t device, sr_ctx** out) {
   if (const char* m = std::getenv("SR_K2_SPLIT_MIN")) ctx->enc.split_min = std::max(0, std::atoi(m));
   if (const char* m = std::getenv("SR_K2_DISPATCH_EVENTS")) ctx->k2_dispatch_events = std::atoi(m) != 0;
   if (const char* m = std::getenv("SR_LIST_HEAD")) ctx->enc.list_head = std::max(0, std::atoi(m));
+  if (const char* m = std::getenv("SR_K2_MAP_REGS")) ctx->k2_map_regs = std::atoi(m) != 0;
   if (const char* m = std::getenv("SR_K2_COOP")) ctx->k2_coop = std::max(0, std::atoi(m));
   *out = ctx;
   return SR_OK;

@@ -15,7 +15,13 @@ Node-order waves ([5] == 2) reuse the fields: [6] placements, [7] visits |
 windows << 32, [8] prologue (F heads) cycles, [9] min + window load,
 [10] placement (window visits), [11] pointer moves (+ far resolution), [14]
 cycles from wave start to the pod records and window 0 in registers, [15] 1
-if the candidate's window visits use 32-bit scaled state.
+if the candidate's window visits use 32-bit scaled state (+2: a cooperative
+block, +16: the candidate is drainable).  Their sections stay far below 2^32
+cycles, and the high halves carry the split of the two sections that wait for
+table rows: [8] >> 32 the prologue's cycles from a batch's first load to its
+last one's return, [11] >> 32 the same for the far resolutions' chunk rounds
+(the rest of the section consumes the rows), [10] >> 32 the pods pending over
+all resolutions (16 bits) and the resolutions (16 bits above).
 The last of the widest runs in the file is summarised (earlier ones are
 warmup; narrower ones are prefix batches of sr_plan_first)."""
 import sys
@@ -37,6 +43,12 @@ def main():
     runs, k0s = load(sys.argv[1])
     last_run = max(range(len(runs)), key=lambda i: (len(runs[i]), i))
     r = runs[last_run].astype(np.int64)
+    nod = r[:, 5] == 2
+    split = np.zeros((len(r), 4), np.int64)  # prologue loads, resolve loads, pending pods, resolutions
+    split[nod] = np.stack([r[nod, 8] >> 32, r[nod, 11] >> 32, (r[nod, 10] >> 32) & 0xffff, r[nod, 10] >> 48], axis=1)
+    for c in (8, 10, 11):
+        r[nod, c] &= 0xffffffff
+    full = r
     k0 = k0s[last_run].astype(np.int64)
     k0 = k0[k0[:, 0] != 0]
     t0 = r[:, 0].min()
@@ -112,7 +124,6 @@ def main():
     st = max(1, (steps[~nodeo] if (~nodeo).any() else steps).sum())
     print("cycles/step by section a,b,c,d,spec-wait:", " ".join("%.0f" % (x / st) for x in tot))
     last = np.argsort(-end)[:8]
-    full = runs[last_run].astype(np.int64)
     cols = ("wave start_us dur_us steps mode | visits placements windows | "
             "cycles: entry->records prologue min+window placement moves | 32-bit (+2: cooperative block) | "
             "resolve (chunk rounds, dead) window-loads")
@@ -128,8 +139,35 @@ def main():
     for c in last:
         row(c)
     print("longest waves: " + cols)
-    for c in np.argsort(-dur, kind="stable")[:8]:
-        row(int(c))
+    longest = [int(c) for c in np.argsort(-dur, kind="stable")[:8]]
+    for c in longest:
+        row(c)
+    if nodeo.any():
+        # the sections that wait for table rows, split: loads returned (first load of a batch -> last return) and
+        # consumed (the rest), for the prefix the host walks before it returns and for the longest waves
+        ok = np.flatnonzero(nodeo & ((full[:, 15] & 16) != 0))
+        first_ok = int(ok[0]) if len(ok) else -1
+        res = full[:, 12] & ((1 << 40) - 1)
+
+        def srow(c):
+            print("  %5d %6.2f %6.2f | %6d | %6d = %6d + %6d | %6d = %6d + %6d | %3d pods in %d resolutions, %d chunk rounds"
+                  % (c, end[c], dur[c], full[c, 14], full[c, 8], split[c, 0], full[c, 8] - split[c, 0], res[c], split[c, 1],
+                     res[c] - split[c, 1], split[c, 2], split[c, 3], (full[c, 12] >> 40) & 0xffff))
+        scols = ("wave end_us dur_us | entry->records | prologue = loads returned + consumed | "
+                 "resolve = loads returned + consumed | pending pods")
+        print("first drainable candidate: %d" % first_ok)
+        print("candidates 0..first_ok: " + scols)
+        for c in range(0, first_ok + 1):
+            if nodeo[c]:
+                srow(c)
+        print("longest waves: " + scols)
+        for c in longest:
+            if nodeo[c]:
+                srow(c)
+        tot = full[nodeo]
+        print("all node-order waves: prologue %d cycles, of them loads returned %.1f %%; resolve %d cycles, of them "
+              "loads returned %.1f %%" % (tot[:, 8].sum(), 100.0 * split[nodeo, 0].sum() / max(1, tot[:, 8].sum()),
+                                          res[nodeo].sum(), 100.0 * split[nodeo, 1].sum() / max(1, res[nodeo].sum())))
 
 
 if __name__ == "__main__":
