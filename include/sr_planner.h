@@ -515,7 +515,9 @@ const char *sr_build_info(void);
  * sr_snapshot_refresh_cached; ABI 9 the sr_timing K2 launch fields; ABI 10
  * sr_plan_sequence; ABI 11 sr_plan_sequence_pdb; sr_explain_pods and
  * sr_explain_candidate were added under ABI 11: two new functions, no struct
- * changed its layout; sr_explain_plan likewise: one more function). */
+ * changed its layout; sr_explain_plan likewise: one more function;
+ * sr_shortfall_pods and sr_shortfall_plan likewise: two functions and one new
+ * output struct, sr_shortfall_out). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -648,6 +650,53 @@ sr_status sr_plan(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluste
 sr_status sr_explain_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
                           const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
                           sr_explain_out *out, uint8_t *out_how /* optional [n_cand] */);
+
+/* "By how much": what a pod that NodeResourcesFit refuses is short of, per
+ * node and reduced over the spot nodes.  With m the mask
+ * sr_explain_pods / sr_explain_plan gives the pod on a node and
+ * R = SR_WHY_PODS | SR_WHY_CPU | SR_WHY_MEMORY | SR_WHY_EPHEMERAL:
+ *   shortfall in cpu / memory / ephemeral   0 when m lacks the bit, else
+ *       request_d + requested_d - allocatable_d (>= 1; requested_d with the
+ *       candidate's earlier pods on that node for sr_shortfall_plan);
+ *   shortfall in pods   0 when m lacks SR_WHY_PODS, else
+ *       pods on the node + earlier pods there + 1 - allowed pods (>= 1),
+ *       INT64_MAX where that does not fit;
+ *   near miss   a node with m != 0 and (m & ~R) == 0: the four checks of
+ *       NodeResourcesFit alone refuse the pod there;
+ *   only-d node   a node whose mask is exactly the bit of dimension d.
+ * SR_WHY_SCALAR is no dimension: a node with it in its mask is no near miss. */
+#define SR_SHORT_CPU       0
+#define SR_SHORT_MEMORY    1
+#define SR_SHORT_EPHEMERAL 2
+#define SR_SHORT_PODS      3
+#define SR_SHORT_COUNT     4
+
+typedef struct {
+  int32_t *near;        /* [n] near-miss nodes; -1 for a fallback pod */
+  int32_t *only_nodes;  /* [n][SR_SHORT_COUNT] nodes whose mask is exactly that one bit */
+  int64_t *only_min;    /* [n][SR_SHORT_COUNT] smallest shortfall among them, 0 when none */
+  int32_t *only_at;     /* [n][SR_SHORT_COUNT] lowest spot position attaining it, -1 when none */
+  int64_t *node_short;  /* optional [n][n_spot][SR_SHORT_COUNT]: every node's shortfalls (0 where the bit is not set,
+                           whatever else refuses the pod there); NULL = not wanted */
+} sr_shortfall_out;
+
+/* sr_explain_pods with the shortfalls, from one device pass.  `why` is
+ * optional; when given it receives exactly what sr_explain_pods writes.  A
+ * fallback pod has near = -1, only_nodes and only_min 0, only_at -1 and
+ * node_short 0.  Arguments, errors and what is left untouched as for
+ * sr_explain_pods; a NULL near, only_nodes, only_min or only_at (or, with
+ * `why`, a NULL required array of it) is SR_ERR_INVALID_ARG. */
+sr_status sr_shortfall_pods(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluster, const int32_t *pods,
+                            int32_t n, sr_explain_out *why /* optional */, sr_shortfall_out *out);
+/* sr_explain_plan with the shortfalls: every array of `out` by the candidate's
+ * local position.  A candidate that is not asked has a fallback pod's values
+ * (near = -1, as feasible = -1 under SR_EXPLAIN_NONE).  Everything else (argument errors, SR_ERR_STATE, the
+ * two ways and out_how, the snapshot restored on every path, no collective) as
+ * for sr_explain_plan. */
+sr_status sr_shortfall_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
+                            const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
+                            sr_explain_out *why /* optional */, sr_shortfall_out *out,
+                            uint8_t *out_how /* optional [n_cand] */);
 
 /* The planning segment as run() executes it (rescheduler.go:228-287): the
  * candidates in order until the first whose plan succeeds (drain + break,

@@ -43,4 +43,30 @@ struct ExplainPlanArgs {
 
 hipError_t launch_explain_plan(const ExplainPlanArgs& a, hipStream_t s);
 
+// sr_shortfall_pods / sr_shortfall_plan: sibling kernels of the two above (k_shortfall in explain.hip,
+// k_shortfall_plan in explain_plan.hip) that take these beside the explain arguments, so the explain kernels'
+// own arguments, registers and LDS stay what they were.  A block leaves its minimum per dimension as a partial
+// and k_shortfall_close takes the partials of a query in block order: no result depends on the order in which
+// blocks or atomics ran.
+constexpr int kShortSums = 8;  // words per queried pod: near, only_nodes[SR_SHORT_COUNT], 3 spare
+constexpr uint64_t kShortNone = ~uint64_t(0);  // no only-d node (a shortfall is at most INT64_MAX)
+
+struct ShortfallArgs {
+  const int64_t* node_left;  // [n_pad] allowed pods - pods (explain_plan.hpp node_left), pads 0
+  int32_t* sums;             // [n_pods][kShortSums], zeroed on the stream before the launch
+  uint64_t* part_min;        // [n_pods][blocks][SR_SHORT_COUNT] a block's smallest only-d shortfall, kShortNone: none
+  int32_t* part_at;          // [n_pods][blocks][SR_SHORT_COUNT] the lowest position attaining it
+  int32_t blocks;            // gridDim.x of the launch
+  int64_t* only_min;         // [n_pods][SR_SHORT_COUNT] written by k_shortfall_close
+  int32_t* only_at;          // [n_pods][SR_SHORT_COUNT]
+  int64_t* node_short;       // [n_pods][n_spot][SR_SHORT_COUNT], nullptr: not wanted
+};
+
+inline int32_t shortfall_blocks(int32_t Wp) { return (Wp + 3) / 4; }  // (kXWaves row words a block)
+hipError_t launch_shortfall(const ExplainArgs& a, const ShortfallArgs& sa, hipStream_t s);
+// (pa.node_slack is not read: the slack is node_left clamped)
+hipError_t launch_shortfall_plan(const ExplainPlanArgs& pa, const ShortfallArgs& sa, hipStream_t s);
+// closes the partials of every query (after the launches above, on the same stream)
+hipError_t launch_shortfall_close(int32_t n_pods, const ShortfallArgs& sa, hipStream_t s);
+
 }  // namespace sr

@@ -122,6 +122,28 @@ void node_slack(const sr_snapshot* snap, int32_t n_pad, std::vector<int32_t>* ou
   }
 }
 
+void node_left(const sr_snapshot* snap, int32_t n_pad, std::vector<int64_t>* out) {
+  out->assign(static_cast<size_t>(n_pad), 0);
+  const size_t n = std::min(snap->nodes.size(), static_cast<size_t>(n_pad));
+  for (size_t i = 0; i < n; ++i) {
+    int64_t left;
+    if (__builtin_sub_overflow(snap->nodes[i].alloc_pods, snap->state[i].npods, &left))
+      left = snap->nodes[i].alloc_pods < 0 ? INT64_MIN : INT64_MAX;
+    (*out)[i] = left;
+  }
+}
+
+void shortfall_node(uint32_t mask, const ExplainPod& p, const int64_t* node_free, int32_t n_pad, int32_t node,
+                    int64_t left, const PlanCtxEntry* e, int64_t out[SR_SHORT_COUNT]) {
+  for (int d = 0; d < 3; ++d) {
+    const int64_t free = node_free[static_cast<size_t>(d) * n_pad + node] - (e ? e->acc[d] : 0);
+    out[SR_SHORT_CPU + d] = (mask >> (WHY_CPU + d) & 1) ? p.req[d] - free : 0;
+  }
+  // the bit says left - earlier < 1, so 1 + earlier - left lies in [1, 2^63 + 2^31]: exact in 64 unsigned bits
+  const uint64_t u = uint64_t(1) + static_cast<uint64_t>(e ? e->pods : 0) - static_cast<uint64_t>(left);
+  out[SR_SHORT_PODS] = (mask >> WHY_PODS & 1) ? static_cast<int64_t>(std::min<uint64_t>(u, INT64_MAX)) : 0;
+}
+
 const PlanCtxEntry* find_ctx(const PlanCtxEntry* lo, const PlanCtxEntry* hi, int32_t node) {
   const PlanCtxEntry* it =
       std::lower_bound(lo, hi, node, [](const PlanCtxEntry& e, int32_t v) { return e.node < v; });

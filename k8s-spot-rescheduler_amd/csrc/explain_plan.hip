@@ -70,7 +70,85 @@ __global__ __launch_bounds__(kXThreads) void k_explain_plan(ExplainPlanArgs pa) 
   explain_reduce(s_part, mask, valid, word, lane, wave, a.n_pad, a.sums + static_cast<size_t>(q) * kExplainSums);
 }
 
+// sr_shortfall_plan: k_explain_plan keeping, per lane, the differences behind the four resource bits (as
+// k_shortfall does for k_explain).  The nodes' pod slack is node_left clamped, so pa.node_slack is not read.  A
+// pad is never touched and holds INT64_MIN in node_free: it is left out before anything is subtracted.
+__global__ __launch_bounds__(kXThreads) void k_shortfall_plan(ExplainPlanArgs pa, ShortfallArgs sa) {
+  __shared__ int s_part[kXWaves][kXCols];
+  __shared__ ShortLds s_short;
+  const ExplainArgs& a = pa.x;
+  const int q = a.pod0 + static_cast<int>(blockIdx.y);
+  const int lane = static_cast<int>(threadIdx.x) & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  const int word = static_cast<int>(blockIdx.x) * kXWaves + wave;
+  const bool live = word < a.Wp;
+  const int node = word * 64 + lane;
+  const bool valid = live && node < a.n_spot;
+  uint32_t mask = 0;
+  int64_t sf[SR_SHORT_COUNT] = {0, 0, 0, 0};
+  if (live) {
+    const ExplainPod p = a.pods[q];
+    bool pods_judged;
+    mask = explain_walk(a, p.cls, word, lane, &pods_judged);
+    const int c0 = pa.ctx_off[q], c1 = pa.ctx_off[q + 1];
+    int touched = 0;
+    int64_t acc[3] = {0, 0, 0};
+    if (c0 < c1) {
+      int lo = c0, hi = c1;
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (pa.ctx[mid].node < word * 64) lo = mid + 1;
+        else hi = mid;
+      }
+      for (int i = lo; i < c1; ++i) {
+        const int en = pa.ctx[i].node;
+        if (en >= word * 64 + 64) break;
+        if (en == node) {
+          touched = pa.ctx[i].pods;
+          for (int d = 0; d < 3; ++d) acc[d] = pa.ctx[i].acc[d];
+        }
+      }
+    }
+    if (valid) {
+      const int64_t left = sa.node_left[node];
+      if (touched > 0 && pods_judged)
+        mask = (mask & ~(1u << WHY_PODS)) | (short_slack(left) - touched < 1 ? 1u << WHY_PODS : 0u);
+      if (p.resources) {
+        for (int d = 0; d < 3; ++d) {
+          const int64_t free = a.node_free[static_cast<size_t>(d) * a.n_pad + node] - acc[d];
+          if (p.req[d] > free) {
+            mask |= 1u << (WHY_CPU + d);
+            sf[SR_SHORT_CPU + d] = p.req[d] - free;
+          }
+        }
+      }
+      if (mask >> WHY_PODS & 1) sf[SR_SHORT_PODS] = short_pods(left, touched);
+      if (a.node_mask) a.node_mask[static_cast<size_t>(q) * a.n_spot + node] = static_cast<uint16_t>(mask);
+      if (sa.node_short) shortfall_store(sa, static_cast<size_t>(q), a.n_spot, node, sf);
+    } else {
+      mask = 0;
+    }
+  }
+  shortfall_wave(&s_short, mask, valid, sf, word, lane, wave);
+  explain_reduce(s_part, mask, valid, word, lane, wave, a.n_pad, a.sums + static_cast<size_t>(q) * kExplainSums);
+  shortfall_block(&s_short, sa, q);
+}
+
 }  // namespace
+
+hipError_t launch_shortfall_plan(const ExplainPlanArgs& a, const ShortfallArgs& sa, hipStream_t s) {
+  const unsigned gx = static_cast<unsigned>(shortfall_blocks(a.x.Wp));
+  if (static_cast<int32_t>(gx) != sa.blocks) return hipErrorInvalidValue;
+  for (int32_t q0 = 0; q0 < a.x.n_pods; q0 += 65535) {  // (gridDim.y)
+    ExplainPlanArgs part = a;
+    part.x.pod0 = q0;
+    hipLaunchKernelGGL(k_shortfall_plan, dim3(gx, static_cast<unsigned>(std::min(65535, a.x.n_pods - q0))),
+                       dim3(kXThreads), 0, s, part, sa);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 hipError_t launch_explain_plan(const ExplainPlanArgs& a, hipStream_t s) {
   const unsigned gx = static_cast<unsigned>((a.x.Wp + kXWaves - 1) / kXWaves);

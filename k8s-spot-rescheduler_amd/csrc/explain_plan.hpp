@@ -56,6 +56,21 @@ void node_slack(const sr_snapshot* snap, int32_t n_pad, std::vector<int32_t>* ou
 uint32_t explain_node_ctx(const ExplainPrograms& x, const ExplainPod& p, const uint64_t* atoms, int32_t Wp,
                           const int64_t* node_free, int32_t n_pad, int32_t node, int32_t slack, const PlanCtxEntry* e);
 
+// sr_shortfall_pods / sr_shortfall_plan: what the node is short of, given the
+// mask explain_node / explain_node_ctx gave it (the statement the shortfall
+// kernels follow).  out[SR_SHORT_*] is 0 where the mask lacks the bit.  cpu /
+// memory / ephemeral: request - (free - acc), which the encoder's ranges keep
+// below 2^63 (requests and node quantities lie in [0, 2^62)).  pods:
+// 1 - (left - earlier pods there), `left` being node_left's value; allowed
+// pods are any int64, so this one saturates at INT64_MAX.
+void shortfall_node(uint32_t mask, const ExplainPod& p, const int64_t* node_free, int32_t n_pad, int32_t node,
+                    int64_t left, const PlanCtxEntry* e, int64_t out[SR_SHORT_COUNT]);
+
+// Allowed pods minus pods of every spot node in 64 bits ([n_pad], pads 0),
+// INT64_MIN where the difference does not fit.  node_slack is this clamped to
+// +-2^30.
+void node_left(const sr_snapshot* snap, int32_t n_pad, std::vector<int64_t>* out);
+
 // The entry of `node` in a sorted list [lo, hi), nullptr: untouched.
 const PlanCtxEntry* find_ctx(const PlanCtxEntry* lo, const PlanCtxEntry* hi, int32_t node);
 

@@ -75,4 +75,91 @@ __device__ __forceinline__ void explain_reduce(int (*s_part)[kXCols], uint32_t m
   }
 }
 
+// --- the shortfall kernels (k_shortfall, k_shortfall_plan) ---
+
+static_assert(kXWaves == 4, "shortfall_blocks (explain_dev.hpp) counts four row words a block");
+
+// The mask bit of a dimension: SR_SHORT_CPU / MEMORY / EPHEMERAL follow WHY_CPU.., SR_SHORT_PODS is WHY_PODS.
+__device__ __forceinline__ uint32_t short_bit(int d) { return d < 3 ? 1u << (WHY_CPU + d) : 1u << WHY_PODS; }
+constexpr uint32_t kShortBits = 1u << WHY_PODS | 1u << WHY_CPU | 1u << WHY_MEMORY | 1u << WHY_EPHEMERAL;
+
+// shortfall_node's pod term: 1 + earlier pods there - left, saturating at INT64_MAX (only read where the bit is set)
+__device__ __forceinline__ int64_t short_pods(int64_t left, int touched) {
+  const uint64_t u = uint64_t(1) + static_cast<uint64_t>(touched) - static_cast<uint64_t>(left);
+  return static_cast<int64_t>(u < static_cast<uint64_t>(INT64_MAX) ? u : static_cast<uint64_t>(INT64_MAX));
+}
+// node_slack's clamp of node_left
+__device__ __forceinline__ int short_slack(int64_t left) {
+  return static_cast<int>(left < -(1 << 30) ? -(1 << 30) : left > (1 << 30) ? (1 << 30) : left);
+}
+
+struct ShortLds {
+  int cnt[kXWaves][1 + SR_SHORT_COUNT];  // near, only_nodes
+  uint64_t min[kXWaves][SR_SHORT_COUNT];
+  int at[kXWaves][SR_SHORT_COUNT];
+};
+
+// The wave's part, before the block's barrier (the one explain_reduce holds): near-miss and only-d nodes by
+// ballot; per dimension the smallest shortfall among the wave's only-d nodes by a 64-bit butterfly (skipped,
+// wave-uniformly, when the wave has none) and the lowest lane attaining it by a second ballot.  A pad is not
+// valid, so it never votes and its sf (zeros: nothing was subtracted for it) is never read.
+__device__ __forceinline__ void shortfall_wave(ShortLds* s, uint32_t mask, bool valid, const int64_t sf[SR_SHORT_COUNT],
+                                               int word, int lane, int wave) {
+  const uint64_t nb = __ballot(valid && mask != 0 && (mask & ~kShortBits) == 0);
+  if (lane == 0) s->cnt[wave][0] = __popcll(nb);
+  for (int d = 0; d < SR_SHORT_COUNT; ++d) {
+    const bool only = valid && mask == short_bit(d);
+    const uint64_t ob = __ballot(only);
+    uint64_t m = kShortNone;
+    int at = -1;
+    if (ob != 0) {
+      const uint64_t key = only ? static_cast<uint64_t>(sf[d]) : kShortNone;
+      m = key;
+      for (int x = 32; x >= 1; x >>= 1) {
+        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(m), x, 64);
+        m = o < m ? o : m;
+      }
+      const uint64_t hit = __ballot(only && key == m);
+      at = word * 64 + __ffsll(static_cast<unsigned long long>(hit)) - 1;
+    }
+    if (lane == 0) {
+      s->cnt[wave][1 + d] = __popcll(ob);
+      s->min[wave][d] = m;
+      s->at[wave][d] = at;
+    }
+  }
+}
+
+// The block's part, after the barrier: the counts as explain_reduce adds its own (one atomic per column and
+// block), the block's minimum per dimension as a partial.  The waves lie in position order, so a strict
+// compare keeps the lowest position among equals.  Every block writes its four partials, so they need no
+// initial value.
+__device__ __forceinline__ void shortfall_block(const ShortLds* s, const ShortfallArgs& sa, int q) {
+  const int tid = static_cast<int>(threadIdx.x);
+  if (tid < 1 + SR_SHORT_COUNT) {
+    int v = 0;
+    for (int w = 0; w < kXWaves; ++w) v += s->cnt[w][tid];
+    if (v != 0) atomicAdd(sa.sums + static_cast<size_t>(q) * kShortSums + tid, v);
+  } else if (tid >= 64 && tid < 64 + SR_SHORT_COUNT) {
+    const int d = tid - 64;
+    uint64_t m = kShortNone;
+    int at = -1;
+    for (int w = 0; w < kXWaves; ++w)
+      if (s->min[w][d] < m) {
+        m = s->min[w][d];
+        at = s->at[w][d];
+      }
+    const size_t o = (static_cast<size_t>(q) * sa.blocks + blockIdx.x) * SR_SHORT_COUNT + d;
+    sa.part_min[o] = m;
+    sa.part_at[o] = at;
+  }
+}
+
+// The lane's node's four shortfalls to node_short: 32 contiguous bytes.
+__device__ __forceinline__ void shortfall_store(const ShortfallArgs& sa, size_t q, int n_spot, int node,
+                                                const int64_t sf[SR_SHORT_COUNT]) {
+  int64_t* dst = sa.node_short + (q * n_spot + node) * SR_SHORT_COUNT;
+  for (int d = 0; d < SR_SHORT_COUNT; ++d) dst[d] = sf[d];
+}
+
 }  // namespace sr

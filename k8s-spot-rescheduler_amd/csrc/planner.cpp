@@ -207,6 +207,7 @@ struct sr_ctx {
   std::vector<sr::PlanCtxEntry> x_centries;  // sr_explain_plan: the context lists, their offsets and the nodes'
                                              //   pod slack as the kernel reads them
   std::vector<int32_t> x_coff, x_slack;
+  std::vector<int64_t> x_left;  // sr_shortfall_*: the nodes' pod slack in 64 bits
   DevBuf x_in, x_out;
   HostBuf hx_in, hx_out;
 };
@@ -1831,8 +1832,22 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
 // stop pods, pod i carries the context list pq->off[i] and the kernel is
 // explain_plan.hip's, which reads the lists and the nodes' pod slack from the
 // same buffer.  `slot` (nullptr: i) is where pod i's results go in `out`.
+// sr_shortfall_pods / sr_shortfall_plan are the same call with `sh`: the
+// sibling kernels (k_shortfall, k_shortfall_plan) run in place of the explain
+// kernels, read the nodes' pod slack in 64 bits (node_left, in the place of
+// node_slack) and leave per-block partials that k_shortfall_close closes on
+// the same stream; `out` gets what it gets without `sh`.
+static void shortfall_none(sr_shortfall_out* sh, size_t o, size_t ns) {  // a fallback pod, or one not asked
+  sh->near[o] = -1;
+  std::fill_n(sh->only_nodes + o * SR_SHORT_COUNT, SR_SHORT_COUNT, 0);
+  std::fill_n(sh->only_min + o * SR_SHORT_COUNT, SR_SHORT_COUNT, int64_t(0));
+  std::fill_n(sh->only_at + o * SR_SHORT_COUNT, SR_SHORT_COUNT, -1);
+  if (sh->node_short) std::fill_n(sh->node_short + o * ns * SR_SHORT_COUNT, ns * SR_SHORT_COUNT, int64_t(0));
+}
+
 static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                         sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr) {
+                         sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr,
+                         sr_shortfall_out* sh = nullptr) {
   if (n == 0) return SR_OK;
   std::vector<int32_t> off(static_cast<size_t>(n) + 1);
   for (int32_t i = 0; i <= n; ++i) off[i] = i;
@@ -1855,6 +1870,7 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
     std::fill_n(out->counts + o * SR_WHY_COUNT, SR_WHY_COUNT, 0);
     if (out->node_mask) std::fill_n(out->node_mask + o * ns, ns, uint16_t(0));
     if (out->fallback) out->fallback[o] = fb ? 1 : 0;
+    if (sh) shortfall_none(sh, o, ns);
   }
   if (na == 0) return SR_OK;
   if (!sr::build_explain(w, &ctx->x_prog) || w.pod_cls.size() != static_cast<size_t>(na) || w.n_pad != w.Wp * 64 ||
@@ -1895,21 +1911,37 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
         ctx->err = "explain: context node out of range";
         return SR_ERR_STATE;
       }
-    sr::node_slack(snap, w.n_pad, &ctx->x_slack);
+    if (!sh) sr::node_slack(snap, w.n_pad, &ctx->x_slack);
     b_ctx = ctx->x_centries.size() * sizeof(sr::PlanCtxEntry);
     b_coff = up8(ctx->x_coff.size() * sizeof(int32_t));
-    b_slack = up8(ctx->x_slack.size() * sizeof(int32_t));
+    if (!sh) b_slack = up8(ctx->x_slack.size() * sizeof(int32_t));
+  }
+  if (sh) {
+    sr::node_left(snap, w.n_pad, &ctx->x_left);
+    b_slack = ctx->x_left.size() * sizeof(int64_t);
   }
   const size_t o_ctx = o_pods + b_pods, o_coff = o_ctx + b_ctx, o_slack = o_coff + b_coff;
   const size_t in_bytes = o_slack + b_slack;
   const size_t b_sums = static_cast<size_t>(na) * sr::kExplainSums * sizeof(int32_t);
-  const size_t out_bytes = b_sums + (out->node_mask ? static_cast<size_t>(na) * ns * sizeof(uint16_t) : 0);
+  // output: sums [| shortfall sums | only_min | only_at | node_short] | masks [| the blocks' partials, which stay
+  // on the device]
+  const int32_t blocks = sr::shortfall_blocks(w.Wp);
+  const size_t b_ssums = sh ? static_cast<size_t>(na) * sr::kShortSums * sizeof(int32_t) : 0;
+  const size_t b_omin = sh ? static_cast<size_t>(na) * SR_SHORT_COUNT * sizeof(int64_t) : 0;
+  const size_t b_oat = sh ? static_cast<size_t>(na) * SR_SHORT_COUNT * sizeof(int32_t) : 0;
+  const size_t b_nshort = sh && sh->node_short ? static_cast<size_t>(na) * ns * SR_SHORT_COUNT * sizeof(int64_t) : 0;
+  const size_t o_ssums = b_sums, o_omin = o_ssums + b_ssums, o_oat = o_omin + b_omin, o_nshort = o_oat + b_oat;
+  const size_t o_masks = o_nshort + b_nshort;
+  const size_t out_bytes = o_masks + (out->node_mask ? static_cast<size_t>(na) * ns * sizeof(uint16_t) : 0);
+  const size_t o_pmin = up8(out_bytes);
+  const size_t b_pmin = sh ? static_cast<size_t>(na) * blocks * SR_SHORT_COUNT * sizeof(uint64_t) : 0;
+  const size_t o_pat = o_pmin + b_pmin, dev_out_bytes = sh ? o_pat + b_pmin / 2 : out_bytes;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
   HIP_TRY(ctx, host_reserve(ctx->hx_in, in_bytes));
   HIP_TRY(ctx, host_reserve(ctx->hx_out, out_bytes));
   HIP_TRY(ctx, dev_reserve(ctx->x_in, in_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_out, out_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_out, dev_out_bytes));
   char* h = static_cast<char*>(ctx->hx_in.p);
   std::memcpy(h, w.atoms.data(), b_atoms);
   std::memcpy(h + o_free, ctx->x_enc.node_free.data(), b_free);
@@ -1919,11 +1951,12 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   if (pq) {
     if (b_ctx) std::memcpy(h + o_ctx, ctx->x_centries.data(), b_ctx);
     std::memcpy(h + o_coff, ctx->x_coff.data(), ctx->x_coff.size() * sizeof(int32_t));
-    std::memcpy(h + o_slack, ctx->x_slack.data(), ctx->x_slack.size() * sizeof(int32_t));
+    if (!sh) std::memcpy(h + o_slack, ctx->x_slack.data(), ctx->x_slack.size() * sizeof(int32_t));
   }
+  if (sh) std::memcpy(h + o_slack, ctx->x_left.data(), b_slack);
   char* d = static_cast<char*>(ctx->x_in.p);
   HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, b_sums, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, b_sums + b_ssums, ctx->stream));
   sr::ExplainArgs a{};
   a.n_spot = n_spot;
   a.n_pad = w.n_pad;
@@ -1935,21 +1968,42 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   a.xops = reinterpret_cast<const int32_t*>(d + o_ops);
   a.pods = reinterpret_cast<const sr::ExplainPod*>(d + o_pods);
   a.sums = static_cast<int32_t*>(ctx->x_out.p);
-  a.node_mask = out->node_mask ? reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->x_out.p) + b_sums) : nullptr;
+  char* dout = static_cast<char*>(ctx->x_out.p);
+  a.node_mask = out->node_mask ? reinterpret_cast<uint16_t*>(dout + o_masks) : nullptr;
+  sr::ShortfallArgs sa{};
+  if (sh) {
+    sa.node_left = reinterpret_cast<const int64_t*>(d + o_slack);
+    sa.sums = reinterpret_cast<int32_t*>(dout + o_ssums);
+    sa.part_min = reinterpret_cast<uint64_t*>(dout + o_pmin);
+    sa.part_at = reinterpret_cast<int32_t*>(dout + o_pat);
+    sa.blocks = blocks;
+    sa.only_min = reinterpret_cast<int64_t*>(dout + o_omin);
+    sa.only_at = reinterpret_cast<int32_t*>(dout + o_oat);
+    sa.node_short = sh->node_short ? reinterpret_cast<int64_t*>(dout + o_nshort) : nullptr;
+  }
   if (pq) {
     sr::ExplainPlanArgs pa{};
     pa.x = a;
     pa.ctx = reinterpret_cast<const sr::PlanCtxEntry*>(d + o_ctx);
     pa.ctx_off = reinterpret_cast<const int32_t*>(d + o_coff);
-    pa.node_slack = reinterpret_cast<const int32_t*>(d + o_slack);
-    HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
+    pa.node_slack = sh ? nullptr : reinterpret_cast<const int32_t*>(d + o_slack);
+    if (sh) HIP_TRY(ctx, sr::launch_shortfall_plan(pa, sa, ctx->stream));
+    else HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
+  } else if (sh) {
+    HIP_TRY(ctx, sr::launch_shortfall(a, sa, ctx->stream));
   } else {
     HIP_TRY(ctx, sr::launch_explain(a, ctx->stream));
   }
+  if (sh) HIP_TRY(ctx, sr::launch_shortfall_close(na, sa, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const int32_t* sums = static_cast<const int32_t*>(ctx->hx_out.p);
-  const uint16_t* masks = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->hx_out.p) + b_sums);
+  const char* hout = static_cast<const char*>(ctx->hx_out.p);
+  const uint16_t* masks = reinterpret_cast<const uint16_t*>(hout + o_masks);
+  const int32_t* ssums = reinterpret_cast<const int32_t*>(hout + o_ssums);
+  const int64_t* omin = reinterpret_cast<const int64_t*>(hout + o_omin);
+  const int32_t* oat = reinterpret_cast<const int32_t*>(hout + o_oat);
+  const int64_t* nshort = reinterpret_cast<const int64_t*>(hout + o_nshort);
   for (int32_t q = 0; q < na; ++q) {
     const int32_t src = w.pod_src[q] - w.pod_base;
     const size_t i = static_cast<size_t>(slot ? slot[src] : src);
@@ -1958,6 +2012,15 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
     out->feasible[i] = s[sr::kExplainFeasible];
     out->first[i] = s[sr::kExplainFirst] > 0 ? w.n_pad - s[sr::kExplainFirst] : -1;
     if (out->node_mask) std::copy_n(masks + q * ns, ns, out->node_mask + i * ns);
+    if (sh) {
+      sh->near[i] = ssums[static_cast<size_t>(q) * sr::kShortSums];
+      std::copy_n(ssums + static_cast<size_t>(q) * sr::kShortSums + 1, SR_SHORT_COUNT, sh->only_nodes + i * SR_SHORT_COUNT);
+      std::copy_n(omin + static_cast<size_t>(q) * SR_SHORT_COUNT, SR_SHORT_COUNT, sh->only_min + i * SR_SHORT_COUNT);
+      std::copy_n(oat + static_cast<size_t>(q) * SR_SHORT_COUNT, SR_SHORT_COUNT, sh->only_at + i * SR_SHORT_COUNT);
+      if (sh->node_short)
+        std::copy_n(nshort + static_cast<size_t>(q) * ns * SR_SHORT_COUNT, ns * SR_SHORT_COUNT,
+                    sh->node_short + i * ns * SR_SHORT_COUNT);
+    }
   }
   return SR_OK;
 }
@@ -1989,6 +2052,21 @@ sr_status sr_explain_candidate(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster*
   return st != SR_OK ? st : rv;
 }
 
+static bool shortfall_out_ok(const sr_shortfall_out* sh) {
+  return sh && sh->near && sh->only_nodes && sh->only_min && sh->only_at;
+}
+
+// An sr_explain_out of the call's own where the caller of sr_shortfall_* wants none.
+struct OwnExplainOut {
+  std::vector<int32_t> feasible, first, counts;
+  sr_explain_out out{};
+  explicit OwnExplainOut(int32_t n) : feasible(std::max(n, 1)), first(std::max(n, 1)), counts(size_t(std::max(n, 1)) * SR_WHY_COUNT) {
+    out.feasible = feasible.data();
+    out.first = first.data();
+    out.counts = counts.data();
+  }
+};
+
 // sr_explain_plan.  The plain contexts (explain_plan.hpp) go through one
 // encode of their stop pods against the base snapshot, one upload, one launch
 // and one download; every other asked candidate through Fork / AddPod /
@@ -1996,9 +2074,10 @@ sr_status sr_explain_candidate(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster*
 // encode hands back as fallback is asked again on its own when the batch held
 // other pods: candidates of one encode share the state word's host-port bits,
 // so only an encode of its own tells "outside the encoded set" for certain.
-sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                          const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how) {
-  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !explain_out_ok(out)) return SR_ERR_INVALID_ARG;
+// (sr_shortfall_plan is this with `sh`)
+static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                              const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how,
+                              sr_shortfall_out* sh) {
   const int32_t nc = cands->n_cand;
   if (nc > 0 && (!cands->cand_pod_off || !cands->cand_pods || !at_pod)) return SR_ERR_INVALID_ARG;
   if (snap->forked) return SR_ERR_STATE;
@@ -2013,9 +2092,10 @@ sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clus
     std::fill_n(out->counts + static_cast<size_t>(c) * SR_WHY_COUNT, SR_WHY_COUNT, 0);
     if (out->node_mask) std::fill_n(out->node_mask + c * ns, ns, uint16_t(0));
     if (out->fallback) out->fallback[c] = 0;
+    if (sh) shortfall_none(sh, static_cast<size_t>(c), ns);
   }
   const int32_t nb = static_cast<int32_t>(pq.batched.size());
-  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data());
+  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data(), sh);
   if (st != SR_OK) return st;
   if (nb > 1)
     for (int32_t i = 0; i < nb; ++i)
@@ -2029,12 +2109,37 @@ sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clus
     // (node_of_pod may be NULL when no asked candidate has an earlier pod)
     const int32_t* map = node_of_pod ? node_of_pod + (off[c] - off[0]) : nullptr;
     for (int32_t k = 0; k < at_pod[c]; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], map[k]);
-    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c);
+    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c, sh);
     const sr_status rv = sr_snapshot_revert(snap);
     if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
   }
   if (out_how) std::copy(pq.how.begin(), pq.how.end(), out_how);
   return SR_OK;
+}
+
+sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                          const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how) {
+  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !explain_out_ok(out)) return SR_ERR_INVALID_ARG;
+  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, out, out_how, nullptr);
+}
+
+sr_status sr_shortfall_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
+                            sr_explain_out* why, sr_shortfall_out* out) {
+  if (!ctx || !snap || !cluster || n < 0 || !shortfall_out_ok(out) || (why && !explain_out_ok(why)) || (n > 0 && !pods))
+    return SR_ERR_INVALID_ARG;
+  if (why) return explain(ctx, snap, cluster, pods, n, why, nullptr, nullptr, out);
+  OwnExplainOut own(n);
+  return explain(ctx, snap, cluster, pods, n, &own.out, nullptr, nullptr, out);
+}
+
+sr_status sr_shortfall_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                            const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* why, sr_shortfall_out* out,
+                            uint8_t* out_how) {
+  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !shortfall_out_ok(out) || (why && !explain_out_ok(why)))
+    return SR_ERR_INVALID_ARG;
+  if (why) return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, why, out_how, out);
+  OwnExplainOut own(cands->n_cand);
+  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, &own.out, out_how, out);
 }
 
 sr_status sr_set_timing(sr_ctx* ctx, int32_t mask) {

@@ -180,6 +180,16 @@ class sr_explain_out(_KeepsArrays):
     _fields_ = [("feasible", P32), ("first", P32), ("counts", P32), ("node_mask", PU16), ("fallback", PU8)]
 
 
+class sr_shortfall_out(_KeepsArrays):
+    _fields_ = [("near", P32), ("only_nodes", P32), ("only_min", P64), ("only_at", P32), ("node_short", P64)]
+
+
+# The dimensions of sr_shortfall_out in index order: SHORT_NAMES[d] is SR_SHORT_<name> = d.
+SHORT_NAMES = ["CPU", "MEMORY", "EPHEMERAL", "PODS"]
+assert len(SHORT_NAMES) == SR_SHORT_COUNT  # noqa: F821 (parsed from the header)
+assert all(_DEF["SR_SHORT_" + name] == d for d, name in enumerate(SHORT_NAMES))
+
+
 # The reasons of sr_explain_pods in bit order: WHY_NAMES[r] is bit 1 << r (SR_WHY_<name>).
 WHY_NAMES = ["UNSCHEDULABLE", "TAINT", "NODE_AFFINITY", "PODS", "CPU", "MEMORY", "EPHEMERAL", "SCALAR", "PORTS",
              "INTER_POD", "SPREAD", "VOLUMES"]
@@ -408,6 +418,12 @@ def _declare_planner(lib):
     lib.sr_explain_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32, ctypes.POINTER(sr_explain_out),
                                     PU8]
     lib.sr_explain_plan.restype = S
+    lib.sr_shortfall_pods.argtypes = [VP, VP, PC, P32, ctypes.c_int32, ctypes.POINTER(sr_explain_out),
+                                      ctypes.POINTER(sr_shortfall_out)]
+    lib.sr_shortfall_pods.restype = S
+    lib.sr_shortfall_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32,
+                                      ctypes.POINTER(sr_explain_out), ctypes.POINTER(sr_shortfall_out), PU8]
+    lib.sr_shortfall_plan.restype = S
     lib.sr_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
     lib.sr_plan.restype = S
     lib.sr_plan_first.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
@@ -443,7 +459,7 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_add_pod", "sr_snapshot_fork", "sr_snapshot_revert", "sr_snapshot_node_state",
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
             "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_explain_pods", "sr_explain_candidate",
-            "sr_explain_plan", "sr_plan", "sr_plan_first", "sr_plan_sequence",
+            "sr_explain_plan", "sr_shortfall_pods", "sr_shortfall_plan", "sr_plan", "sr_plan_first", "sr_plan_sequence",
             "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",
             "sr_comm_init_shm"]

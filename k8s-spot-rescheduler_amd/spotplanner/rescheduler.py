@@ -432,3 +432,102 @@ def explainPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapsho
     cand_off[1:] = np.cumsum([len(c) for c in candidates])
     return explain_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
                                np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod, node_mask)
+
+
+@dataclass
+class ShortfallResult:
+    """sr_shortfall_out for n pods: what each pod NodeResourcesFit refuses is short of (capi.SR_SHORT_* dimensions)."""
+    near: np.ndarray                  # [n] nodes only NodeResourcesFit's four checks refuse; -1 for a fallback pod
+    only_nodes: np.ndarray            # [n][SR_SHORT_COUNT] nodes whose mask is exactly that dimension's bit
+    only_min: np.ndarray              # [n][SR_SHORT_COUNT] smallest shortfall among them, 0 when none
+    only_at: np.ndarray               # [n][SR_SHORT_COUNT] lowest spot position attaining it, -1 when none
+    node_short: Optional[np.ndarray]  # [n][n_spot][SR_SHORT_COUNT] every node's shortfalls (None: not asked for)
+
+    def closest(self, i: int = 0) -> dict:
+        """{dimension name: (shortfall, spot position)} of pod i over the nodes short of that dimension alone."""
+        return {name: (int(self.only_min[i][d]), int(self.only_at[i][d]))
+                for d, name in enumerate(capi.SHORT_NAMES) if self.only_at[i][d] >= 0}
+
+
+def _shortfall_out(n: int, n_spot: int, node_short: bool):
+    m = max(n, 1)
+    near = np.full(m, -1, np.int32)
+    only_nodes = np.zeros((m, capi.SR_SHORT_COUNT), np.int32)
+    only_min = np.zeros((m, capi.SR_SHORT_COUNT), np.int64)
+    only_at = np.full((m, capi.SR_SHORT_COUNT), -1, np.int32)
+    short = np.zeros((m, max(n_spot, 1), capi.SR_SHORT_COUNT), np.int64) if node_short else None
+    o = capi.sr_shortfall_out(capi.ptr(near, capi.P32), capi.ptr(only_nodes, capi.P32), capi.ptr(only_min, capi.P64),
+                              capi.ptr(only_at, capi.P32), capi.ptr(short, capi.P64) if node_short else None)
+    res = ShortfallResult(near[:n], only_nodes[:n], only_min[:n], only_at[:n],
+                          short[:n, :n_spot] if node_short else None)
+    return o, res
+
+
+def shortfall_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, pods: np.ndarray,
+                     node_short: bool = True, node_mask: bool = True, why: bool = True):
+    """sr_shortfall_pods over caller-built arrays: (ExplainResult or None when `why` is False, ShortfallResult)."""
+    lib = predicateChecker.lib
+    pods = np.ascontiguousarray(pods, np.int32)
+    n_spot = lib.sr_snapshot_num_nodes(snapshot_handle)
+    o, res = _explain_out(len(pods), n_spot, node_mask) if why else (None, None)
+    so, short = _shortfall_out(len(pods), n_spot, node_short)
+    st = lib.sr_shortfall_pods(predicateChecker.handle, snapshot_handle, cluster_ptr, capi.ptr(pods, capi.P32),
+                               len(pods), ctypes.byref(o) if why else None, ctypes.byref(so))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_shortfall_pods: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    return res, short
+
+
+def shortfall_plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
+                          cand_pods: np.ndarray, at_pod: np.ndarray, node_of_pod: np.ndarray,
+                          node_short: bool = True, node_mask: bool = True, why: bool = True):
+    """sr_shortfall_plan, arguments as explain_plan_arrays: (ExplainResult with `how`, ShortfallResult); without
+    `why` the first is an ExplainResult that carries `how` alone."""
+    lib = predicateChecker.lib
+    cand_off = np.ascontiguousarray(cand_off, np.int32)
+    cand_pods = np.ascontiguousarray(cand_pods, np.int32)
+    at_pod = np.ascontiguousarray(at_pod, np.int32)
+    if node_of_pod is not None:
+        node_of_pod = np.ascontiguousarray(node_of_pod, np.int32)
+    n = len(cand_off) - 1
+    if len(at_pod) != n:
+        raise ValueError("at_pod needs one entry per candidate")
+    n_spot = lib.sr_snapshot_num_nodes(snapshot_handle)
+    c = capi.sr_candidates(n, capi.ptr(cand_off, capi.P32), capi.ptr(cand_pods, capi.P32), None)
+    o, res = _explain_out(n, n_spot, node_mask) if why else (None, ExplainResult(None, None, None, None, None, n_spot))
+    so, short = _shortfall_out(n, n_spot, node_short)
+    how = np.zeros(max(n, 1), np.uint8)
+    st = lib.sr_shortfall_plan(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                               capi.ptr(at_pod, capi.P32),
+                               capi.ptr(node_of_pod, capi.P32) if node_of_pod is not None else None,
+                               ctypes.byref(o) if why else None, ctypes.byref(so), capi.ptr(how, capi.PU8))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_shortfall_plan: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    res.how = how[:n]
+    return res, short
+
+
+def shortfallPods(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes, pods: Sequence[Pod],
+                  node_short: bool = True, node_mask: bool = True):
+    """explainPods with "by how much": (ExplainResult, ShortfallResult) from one device pass."""
+    _check_order(spotSnapshot, nodes)
+    enc = spotSnapshot.encode_pods(list(pods))
+    return shortfall_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, np.arange(len(pods), dtype=np.int32),
+                            node_short, node_mask)
+
+
+def shortfallPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                  candidates: Sequence[Sequence[Pod]], plan, node_short: bool = True, node_mask: bool = True):
+    """explainPlan with "by how much" for every stuck candidate of `plan`: (ExplainResult, ShortfallResult)."""
+    _check_order(spotSnapshot, nodes)
+    flat = [p for c in candidates for p in c]
+    enc = spotSnapshot.encode_pods(flat)
+    cand_off = np.zeros(len(candidates) + 1, np.int32)
+    cand_off[1:] = np.cumsum([len(c) for c in candidates])
+    return shortfall_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
+                                 np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod, node_short,
+                                 node_mask)

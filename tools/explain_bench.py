@@ -22,7 +22,14 @@ failing candidates, how many stop at a pod k > 0, how many went each way
 not in context; mask == 0 is checked against the oracle forked and filled the
 same way, and (a) against (b) field for field.
 
-  python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan]
+--shortfall times sr_shortfall_pods on the same failing pods (with --plan:
+sr_shortfall_plan on the same tick) beside its explain sibling, in one process:
+counts only, with the per-node masks, and with node_short; the ratio of the
+counts-only calls is the cost of asking "by how much" on top of "why".  `why`
+is checked against the sibling array for array and the reductions against
+numpy over node_mask / node_short.
+
+  python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan] [--shortfall]
 """
 import argparse
 import json
@@ -41,7 +48,7 @@ from sequence_ref import from_synth  # noqa: E402
 from spotplanner import capi  # noqa: E402
 from spotplanner.planner import PredicateChecker  # noqa: E402
 from spotplanner.rescheduler import (explain_arrays, explain_candidate_arrays, explain_plan_arrays,  # noqa: E402
-                                     plan_arrays)
+                                     plan_arrays, shortfall_arrays, shortfall_plan_arrays)
 from spotplanner.synth import SynthCluster  # noqa: E402
 
 
@@ -125,6 +132,89 @@ def plan_mode(args, ck, lib, config):
     return line
 
 
+def reductions_follow(why, short, rows):
+    """near / only_nodes / only_min / only_at of `rows` recomputed with numpy from node_mask and node_short."""
+    R = capi.SR_WHY_PODS | capi.SR_WHY_CPU | capi.SR_WHY_MEMORY | capi.SR_WHY_EPHEMERAL
+    bits = (capi.SR_WHY_CPU, capi.SR_WHY_MEMORY, capi.SR_WHY_EPHEMERAL, capi.SR_WHY_PODS)
+    for i in rows:
+        m, s = why.node_mask[i].astype(np.int64), short.node_short[i]
+        if why.fallback[i]:
+            if short.near[i] != -1 or s.any():
+                return False
+            continue
+        if short.near[i] != int(np.sum((m != 0) & ((m & ~R) == 0))):
+            return False
+        for d, bit in enumerate(bits):
+            at = np.flatnonzero(m == bit)
+            lo = int(s[at, d].min()) if len(at) else 0
+            pos = int(at[np.argmax(s[at, d] == lo)]) if len(at) else -1
+            if (short.only_nodes[i][d], short.only_min[i][d], short.only_at[i][d]) != (len(at), lo, pos):
+                return False
+            if ((s[:, d] != 0) != ((m & bit) != 0)).any():
+                return False
+    return True
+
+
+def shortfall_mode(args, ck, lib, config):
+    """--shortfall: sr_shortfall_pods (with --plan: sr_shortfall_plan) beside its explain sibling, in one process
+    on the same queries: counts only, with the per-node masks, and with node_short as well."""
+    inp = from_synth(SynthCluster(config))
+    h = inp.product_snapshot()
+    off, cp = inp.cand_off, inp.cand_pods
+    try:
+        plan = plan_arrays(ck, h, inp.ptr, off, cp)
+        status, mapping = np.array(plan.status, np.int32), np.array(plan.node_of_pod, np.int32)
+        failing = [c for c in range(len(status)) if status[c] >= 0]
+        stops = np.array([cp[off[c] + status[c]] for c in failing], np.int32)
+        if args.plan:
+            def explain(mask):
+                return explain_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping, node_mask=mask)
+
+            def shortfall(mask, node_short):
+                return shortfall_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping, node_short=node_short,
+                                             node_mask=mask)
+            rows = failing
+        else:
+            def explain(mask):
+                return explain_arrays(ck, h, inp.ptr, stops, node_mask=mask)
+
+            def shortfall(mask, node_short):
+                return shortfall_arrays(ck, h, inp.ptr, stops, node_short=node_short, node_mask=mask)
+            rows = range(len(stops))
+        want = explain(True)
+        why, short = shortfall(True, True)
+        same = all(np.array_equal(getattr(why, f), getattr(want, f))
+                   for f in ("feasible", "first", "counts", "fallback", "node_mask"))
+        _, bare = shortfall(False, False)
+        same_bare = all(np.array_equal(getattr(bare, f), getattr(short, f))
+                        for f in ("near", "only_nodes", "only_min", "only_at"))
+        judged = [i for i in rows if not why.fallback[i]]
+        line = dict(config=config, mode="shortfall_plan" if args.plan else "shortfall", n_failing=len(failing),
+                    n_spot=len(inp.spot), pairs=len(failing) * len(inp.spot), reps=args.reps,
+                    why_equals_explain=bool(same), counts_only_equals_full=bool(same_bare),
+                    reductions_follow_from_node_short=bool(reductions_follow(why, short, rows)),
+                    queries_with_a_near_miss=int(sum(1 for i in judged if short.near[i] > 0)),
+                    only_nodes={name: int(short.only_nodes[judged, d].sum()) for d, name in enumerate(capi.SHORT_NAMES)},
+                    node_short_mib=round(len(rows) * len(inp.spot) * 32 / 2 ** 20, 1))
+        del want, why, short, bare
+        for name, fn in (("explain_counts_only", lambda: explain(False)),
+                         ("explain_with_node_mask", lambda: explain(True)),
+                         ("shortfall_counts_only", lambda: shortfall(False, False)),
+                         ("shortfall_with_node_mask", lambda: shortfall(True, False)),
+                         ("shortfall_with_node_short", lambda: shortfall(True, True))):
+            print("# timing " + name, file=sys.stderr, flush=True)
+            m = median_of(fn, args.reps)
+            line.update({"ms_%s_median" % name: m[0], "ms_%s_min" % name: m[1], "ms_%s_max" % name: m[2]})
+        if line["ms_explain_counts_only_median"] > 0:
+            line["ratio_shortfall_over_explain_counts_only"] = round(
+                line["ms_shortfall_counts_only_median"] / line["ms_explain_counts_only_median"], 2)
+            line["ratio_shortfall_over_explain_with_node_mask"] = round(
+                line["ms_shortfall_with_node_mask_median"] / line["ms_explain_with_node_mask_median"], 2)
+    finally:
+        lib.sr_snapshot_destroy(h)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="3")
@@ -132,12 +222,15 @@ def main():
     ap.add_argument("--no-oracle", action="store_true")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     ap.add_argument("--plan", action="store_true", help="time sr_explain_plan against the per-candidate loop")
+    ap.add_argument("--shortfall", action="store_true",
+                    help="time sr_shortfall_pods (with --plan: sr_shortfall_plan) beside its explain sibling")
     args = ap.parse_args()
     ck = PredicateChecker(0)
     lib = capi.load_planner()
     for config in [int(x) for x in args.configs.split(",")]:
-        if args.plan:
-            text = json.dumps(plan_mode(args, ck, lib, config))
+        if args.shortfall or args.plan:
+            text = json.dumps(shortfall_mode(args, ck, lib, config) if args.shortfall
+                              else plan_mode(args, ck, lib, config))
             print(text, flush=True)
             if args.out:
                 with open(args.out, "a") as f:

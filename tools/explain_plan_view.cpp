@@ -98,3 +98,100 @@ sr_status sr_explain_plan_view(const sr_cluster* cluster, const sr_snapshot* sna
 }
 
 }  // extern "C"
+
+namespace {
+
+// `pods` as candidates of their own against `snap`, tags on; query i (into pods) with the context list
+// [off[i], off[i + 1]) of `entries` (off == nullptr: no contexts): every node's mask by explain_node_ctx and its
+// shortfalls by shortfall_node, into row slot[i] (nullptr: i) of node_mask / node_short; status[i] the encode's.
+sr_status shortfall_rows(const sr_cluster* cluster, const sr_snapshot* snap, const int32_t* pods, int32_t n,
+                         const int32_t* off, const sr::PlanCtxEntry* entries, const int32_t* slot, uint16_t* node_mask,
+                         int64_t* node_short, std::vector<int32_t>* status) {
+  status->assign(static_cast<size_t>(n), SR_CAND_OK);
+  if (n == 0) return SR_OK;
+  const size_t ns = snap->nodes.size();
+  std::vector<int32_t> coff(static_cast<size_t>(n) + 1);
+  for (int32_t i = 0; i <= n; ++i) coff[i] = i;
+  const sr_candidates cands{n, coff.data(), pods, nullptr};
+  sr::EncoderCache cache;
+  cache.want_why = true;
+  sr::Workload w;
+  std::string err;
+  sr_status st = sr::encode_workload(&cache, snap, cluster, &cands, &w, &err);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < n; ++i) (*status)[i] = w.status_host[i];
+  const int32_t na = static_cast<int32_t>(w.pod_src.size());
+  if (na == 0) return SR_OK;
+  sr::ExplainPrograms x;
+  std::vector<sr::ExplainPod> xp;
+  if (!sr::build_explain(w, &x) || w.pod_cls.size() != static_cast<size_t>(na)) return SR_ERR_STATE;
+  sr::explain_pods(w, &xp);
+  std::vector<int32_t> slack;
+  std::vector<int64_t> left;
+  sr::node_slack(snap, std::max(w.n_pad, static_cast<int32_t>(ns)), &slack);
+  sr::node_left(snap, std::max(w.n_pad, static_cast<int32_t>(ns)), &left);
+  for (int32_t q = 0; q < na; ++q) {
+    const int32_t i = w.pod_src[q] - w.pod_base;
+    const sr::PlanCtxEntry *lo = off ? entries + off[i] : nullptr, *hi = off ? entries + off[i + 1] : nullptr;
+    const size_t row = static_cast<size_t>(slot ? slot[i] : i) * ns;
+    for (int32_t node = 0; node < static_cast<int32_t>(ns); ++node) {
+      const sr::PlanCtxEntry* e = off ? sr::find_ctx(lo, hi, node) : nullptr;
+      const uint32_t m = sr::explain_node_ctx(x, xp[q], w.atoms.data(), w.Wp, cache.node_free.data(), w.n_pad, node,
+                                              slack[node], e);
+      node_mask[row + node] = static_cast<uint16_t>(m);
+      sr::shortfall_node(m, xp[q], cache.node_free.data(), w.n_pad, node, left[node], e,
+                         node_short + (row + node) * SR_SHORT_COUNT);
+    }
+  }
+  return SR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// sr_shortfall_pods on the host: node_mask[n][n_spot], node_short[n][n_spot][SR_SHORT_COUNT] and fallback[n] of
+// `pods` against the snapshot as it is (a fallback pod: zeros), by explain_node and shortfall_node.
+sr_status sr_shortfall_pods_view(const sr_cluster* cluster, const sr_snapshot* snap, const int32_t* pods, int32_t n,
+                                 uint16_t* node_mask, int64_t* node_short, uint8_t* fallback) {
+  if (!cluster || !snap || n < 0 || (n > 0 && !pods) || !node_mask || !node_short || !fallback)
+    return SR_ERR_INVALID_ARG;
+  const size_t ns = snap->nodes.size();
+  std::fill_n(node_mask, static_cast<size_t>(n) * ns, uint16_t(0));
+  std::fill_n(node_short, static_cast<size_t>(n) * ns * SR_SHORT_COUNT, int64_t(0));
+  std::vector<int32_t> status;
+  const sr_status st = shortfall_rows(cluster, snap, pods, n, nullptr, nullptr, nullptr, node_mask, node_short, &status);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < n; ++i) fallback[i] = status[i] == SR_CAND_FALLBACK ? 1 : 0;
+  return SR_OK;
+}
+
+// sr_shortfall_plan's batched pass on the host: how[n_cand] as sr_explain_plan_view gives it, and for the batched
+// candidates node_mask[n_cand][n_spot], node_short[n_cand][n_spot][SR_SHORT_COUNT] and fallback[n_cand] in the
+// context of their earlier pods (others: zeros).
+sr_status sr_shortfall_plan_view(const sr_cluster* cluster, const sr_snapshot* snap, const sr_candidates* cands,
+                                 const int32_t* at_pod, const int32_t* node_of_pod, uint8_t* how, uint16_t* node_mask,
+                                 int64_t* node_short, uint8_t* fallback) {
+  if (!cluster || !snap || !cands || !at_pod || !how || !node_mask || !node_short || !fallback) return SR_ERR_INVALID_ARG;
+  sr::PlanQueries pq;
+  sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
+  if (st != SR_OK) return st;
+  const int32_t nc = cands->n_cand, nb = static_cast<int32_t>(pq.batched.size());
+  const size_t ns = snap->nodes.size();
+  std::copy(pq.how.begin(), pq.how.end(), how);
+  std::fill_n(node_mask, static_cast<size_t>(nc) * ns, uint16_t(0));
+  std::fill_n(node_short, static_cast<size_t>(nc) * ns * SR_SHORT_COUNT, int64_t(0));
+  std::fill_n(fallback, nc, uint8_t(0));
+  std::vector<int32_t> status;
+  st = shortfall_rows(cluster, snap, pq.pods.data(), nb, pq.off.data(), pq.entries.data(), pq.batched.data(), node_mask,
+                      node_short, &status);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < nb; ++i) {
+    if (status[i] != SR_CAND_FALLBACK) continue;
+    if (nb > 1) how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
+    else fallback[pq.batched[i]] = 1;
+  }
+  return SR_OK;
+}
+
+}  // extern "C"
