@@ -510,6 +510,7 @@ struct K2Stats {
   uint32_t n_spec_miss = 0, n_min = 0, n_far = 0;
   uint64_t cyc_a = 0, cyc_b = 0, cyc_c = 0, cyc_d = 0;
   uint64_t cyc_rec = 0;  // node order (profile builds): wave entry -> pod records in registers
+  uint64_t cyc_fh = 0;   // node order (profile builds): the first F-head load is issued (0: the wave loads none)
   uint32_t narrow = 0;   // node order: the candidate's window visits use 32-bit scaled state
   uint64_t cyc_res = 0;  // node order: far-pointer resolution cycles (part of cyc_b) | chunk rounds << 40 | pods
                          // found dead << 56
@@ -885,6 +886,85 @@ static_assert(kNH == 2 || kNH == 4 || kNH == 8, "head words per pod: a power of 
 constexpr int kNHS = kNH + 1;      // LDS stride per pod (odd number of words: conflict-free b64 reads)
 constexpr int kFar = 64 * kNH;     // pointer sentinel: next feasible node lies at or beyond the head, unresolved
 
+// A K2 wave's view of the workload.  DevWorkload is read in place from the
+// kernel-argument segment, which makes every field a scalar load in front of
+// its use, waited for on the spot: on a wave's dependent chain those are
+// serial round trips with nothing else to issue.  The fields a node-order
+// wave touches on its chain form the workload's header (kernels.hpp); the
+// wave fetches it once at entry with one vector load, lane i holding word i,
+// together with the changed-node table, and every later use is a v_readlane
+// of a constant lane: no memory access, and nothing the compiler can turn
+// back into a scalar load.  `k` is the workload in place, for what is read
+// once off the chain (the work-list entry, the once-per-run duties).
+#define SR_HW(f) static_cast<int>(offsetof(DevWorkload, f) / 4)
+struct K2W {
+  const DevWorkload& k;
+  uint32_t hdr;  // lane i: word i of the header
+  uint64_t dt;   // lane i: dirty_tab[i] (K0-less runs)
+  // lane 16 f + p: word 1 + f of node patch p -- free cpu, memory, ephemeral, state bits (K0-less runs; fetched
+  // by the wave that plans a candidate in node order, with its pod records: fetch_patches)
+  mutable uint64_t pt = 0;
+  __device__ __forceinline__ explicit K2W(const DevWorkload& kk) : k(kk) {
+    const int lane = threadIdx.x & 63;
+    hdr = reinterpret_cast<const uint32_t*>(&kk)[lane];
+    dt = static_cast<uint64_t>(kk.dirty_tab[lane]);
+  }
+  __device__ __forceinline__ void fetch_patches() const {
+    const int lane = threadIdx.x & 63, nd = n_dirty();
+    // (nd <= 16 patches of kNodePatchU64 words: inside node_patch)
+    if (nd > 0 && (lane & 15) < nd)
+      pt = ptr<const uint64_t*>(SR_HW(node_patch))[(lane & 15) * kNodePatchU64 + 1 + (lane >> 4)];
+  }
+  __device__ __forceinline__ uint32_t word(int i) const {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hdr), i));
+  }
+  // (a pointer rebuilt from two words has lost its address space: said to be global memory again, so that
+  // what goes through it are global loads and stores, not flat ones)
+  template <typename P>
+  __device__ __forceinline__ P ptr(int i) const {
+    typedef __attribute__((address_space(1))) std::remove_pointer_t<P>* G;
+    return (P)(G)(static_cast<uint64_t>(word(i)) | static_cast<uint64_t>(word(i + 1)) << 32);
+  }
+#define SR_HF_I(name)                                                     \
+  __device__ __forceinline__ int32_t name() const {                       \
+    static_assert(SR_HW(name) < kHdrWords, "a field of the wave header"); \
+    return static_cast<int32_t>(word(SR_HW(name)));                       \
+  }
+#define SR_HF_P(type, name)                                                   \
+  __device__ __forceinline__ type name() const {                              \
+    static_assert(SR_HW(name) + 1 < kHdrWords, "a field of the wave header"); \
+    return ptr<type>(SR_HW(name));                                            \
+  }
+  SR_HF_I(Wp) SR_HF_I(k0_skip) SR_HF_I(n_dirty) SR_HF_I(s_head_only) SR_HF_I(k2_narrow) SR_HF_I(k2_excl)
+  SR_HF_I(n_pad) SR_HF_I(k2_map_regs) SR_HF_I(n_coop) SR_HF_I(cand_floor) SR_HF_I(n_list_head)
+  SR_HF_P(const uint64_t*, pod_rec) SR_HF_P(const uint64_t*, node_rec) SR_HF_P(const uint64_t*, S)
+  SR_HF_P(const uint64_t*, atoms) SR_HF_P(const int32_t*, cls_prog8) SR_HF_P(const uint64_t*, pod_ext)
+  SR_HF_P(const int64_t*, node_scal) SR_HF_P(int32_t*, out_node) SR_HF_P(int32_t*, out_status)
+  SR_HF_P(uint32_t*, out_bytes) SR_HF_P(uint32_t*, out_cycles) SR_HF_P(int32_t*, d_min) SR_HF_P(uint64_t*, res_stat)
+  SR_HF_P(uint64_t*, res_map) SR_HF_P(uint64_t*, prof)
+#undef SR_HF_I
+#undef SR_HF_P
+  __device__ __forceinline__ uint32_t s_empty_off() const { return word(SR_HW(s_empty_off)); }
+  __device__ __forceinline__ uint32_t seq() const { return word(SR_HW(seq)); }
+  __device__ __forceinline__ uint64_t swap_mask() const {
+    return static_cast<uint64_t>(word(SR_HW(swap_mask))) | static_cast<uint64_t>(word(SR_HW(swap_mask) + 1)) << 32;
+  }
+  // changed node p (wave-uniform): its spot position, its pods_left, its free value in dimension d, word
+  // 1 + f of its patch record
+  __device__ __forceinline__ int dirty_node(int p) const {
+    return __builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(dt)), 48 + p);
+  }
+  __device__ __forceinline__ int dirty_left(int p) const {
+    return __builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(dt >> 32)), 48 + p);
+  }
+  __device__ __forceinline__ int64_t dirty_free(int p, int d) const {
+    return static_cast<int64_t>(readlane64(dt, 16 * d + p));
+  }
+  __device__ __forceinline__ uint64_t patch_word(int p, int f) const { return readlane64(pt, 16 * f + p); }
+};
+static_assert(SR_HW(seq) < kHdrWords && SR_HW(swap_mask) + 1 < kHdrWords && SR_HW(s_empty_off) < kHdrWords,
+              "fields of the wave header");
+
 // Word `wd` of the lane's own F row, straight from the tables.
 __device__ __forceinline__ uint64_t f_word_far(const uint64_t* __restrict__ tab, uint64_t r01, uint64_t r23, int wd) {
   return tab[static_cast<uint32_t>(r01) + wd] & tab[static_cast<uint32_t>(r01 >> 32) + wd] &
@@ -892,26 +972,26 @@ __device__ __forceinline__ uint64_t f_word_far(const uint64_t* __restrict__ tab,
 }
 
 // The S part alone, from the lane's class program (s_head_only).
-__device__ __forceinline__ uint64_t f_word_prog_s(const DevWorkload& w, const int32_t* pg, int wd) {
+__device__ __forceinline__ uint64_t f_word_prog_s(const K2W& w, const int32_t* pg, int wd) {
   int op[8];
   uint64_t v[8];
 #pragma unroll
   for (int u = 0; u < 8; ++u) op[u] = pg[u];
 #pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = op[u] >= 0 ? w.atoms[static_cast<size_t>(op[u] >> 2) * w.Wp + wd] : 0ull;
+  for (int u = 0; u < 8; ++u) v[u] = op[u] >= 0 ? w.atoms()[static_cast<size_t>(op[u] >> 2) * w.Wp() + wd] : 0ull;
   return eval_prog8(op, v);
 }
 
 // The same word with the S part evaluated from the lane's class program (in
 // LDS) when K0 wrote only the heads of the S rows (s_head_only).
-__device__ __forceinline__ uint64_t f_word_prog(const DevWorkload& w, const uint64_t* __restrict__ tab,
+__device__ __forceinline__ uint64_t f_word_prog(const K2W& w, const uint64_t* __restrict__ tab,
                                                 const int32_t* pg, uint64_t r01, uint64_t r23, int wd) {
   int op[8];
   uint64_t v[8];
 #pragma unroll
   for (int u = 0; u < 8; ++u) op[u] = pg[u];
 #pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = op[u] >= 0 ? w.atoms[static_cast<size_t>(op[u] >> 2) * w.Wp + wd] : 0ull;
+  for (int u = 0; u < 8; ++u) v[u] = op[u] >= 0 ? w.atoms()[static_cast<size_t>(op[u] >> 2) * w.Wp() + wd] : 0ull;
   return eval_prog8(op, v) & tab[static_cast<uint32_t>(r01 >> 32) + wd] & tab[static_cast<uint32_t>(r23) + wd] &
          tab[static_cast<uint32_t>(r23 >> 32) + wd];
 }
@@ -921,32 +1001,19 @@ __device__ __forceinline__ uint64_t f_word_prog(const DevWorkload& w, const uint
 // the S word and the nodes' current free values (fitsRequest per dimension;
 // an all-zero request skips it).  Every other node's T bits stand: its free
 // value is the one the rows were built from, and no node value then lay
-// between a request and its row's threshold.
-__device__ __forceinline__ uint64_t fix_dirty(const DevWorkload& w, uint64_t f, uint64_t s, int wd, int64_t rc,
-                                              int64_t rm, int64_t re, bool zero) {
-  for (int p = 0; p < w.n_dirty; ++p) {
-    const int n = w.dirty_node[p];
-    if ((n >> 6) != wd) continue;
+// between a request and its row's threshold.  `fm`: the pod's fit mask of the
+// changed nodes (bit p: it fits changed node p -- k2_node_order's dfit, the
+// same compares made once per pod); the nodes come from the wave's table, a
+// wave-uniform loop without a branch or a memory access.
+__device__ __forceinline__ uint64_t fix_dirty(const K2W& w, uint64_t f, uint64_t s, int wd, uint32_t fm) {
+  const int nd = w.n_dirty();
+  for (int p = 0; p < nd; ++p) {
+    const int n = w.dirty_node(p);
     const uint64_t bit = 1ull << (n & 63);
-    const bool fits = zero || (w.dirty_free[p][0] >= rc && w.dirty_free[p][1] >= rm && w.dirty_free[p][2] >= re);
-    f = fits ? (f | (s & bit)) : (f & ~bit);
+    const uint64_t g = (fm >> p) & 1 ? (f | (s & bit)) : (f & ~bit);
+    f = (n >> 6) == wd ? g : f;
   }
   return f;
-}
-
-// A K0-less run: lane i's base record of window W from node_patch when node
-// 64 W + i changed since the node section was written.
-__device__ __forceinline__ void window_patch(const DevWorkload& w, int W, int lane, int64_t& ncpu, int64_t& nmem,
-                                             int64_t& neph, uint64_t& nport, int& nleft) {
-  for (int p = 0; p < w.n_node_patch; ++p) {
-    const uint64_t* pr = w.node_patch + static_cast<size_t>(p) * kNodePatchU64;
-    if (static_cast<int>(pr[0]) != 64 * W + lane) continue;
-    ncpu = static_cast<int64_t>(pr[1]);
-    nmem = static_cast<int64_t>(pr[2]);
-    neph = static_cast<int64_t>(pr[3]);
-    nport = pr[4];
-    nleft = static_cast<int>(static_cast<int64_t>(pr[5]));
-  }
 }
 
 // 32-bit value of lane `src` (per-lane source index), through the LDS crossbar.
@@ -975,6 +1042,30 @@ __device__ __forceinline__ int writelane(int v, int x, int k) {
   return v;
 }
 #pragma clang diagnostic pop
+__device__ __forceinline__ uint64_t writelane64(uint64_t v, uint64_t x, int k) {
+  const int lo = writelane(static_cast<int>(static_cast<uint32_t>(v)), static_cast<int>(static_cast<uint32_t>(x)), k);
+  const int hi = writelane(static_cast<int>(static_cast<uint32_t>(v >> 32)), static_cast<int>(static_cast<uint32_t>(x >> 32)), k);
+  return static_cast<uint64_t>(static_cast<uint32_t>(hi)) << 32 | static_cast<uint32_t>(lo);
+}
+// A K0-less run: lane i's base record of window W from the node patches when
+// node 64 W + i changed since the node section was written.  The patches are
+// in the wave's registers (K2W): a wave-uniform loop, a scalar compare per
+// patch, and for a node of the window five lane writes -- no load, and no
+// wait for the window's own records.
+__device__ __forceinline__ void window_patch(const K2W& w, int W, int64_t& ncpu, int64_t& nmem, int64_t& neph,
+                                             uint64_t& nport, int& nleft) {
+  const int nd = w.n_dirty();
+  for (int p = 0; p < nd; ++p) {
+    const int n = w.dirty_node(p);
+    if ((n >> 6) != W) continue;  // wave-uniform
+    const int k = n & 63;
+    ncpu = static_cast<int64_t>(writelane64(static_cast<uint64_t>(ncpu), w.patch_word(p, 0), k));
+    nmem = static_cast<int64_t>(writelane64(static_cast<uint64_t>(nmem), w.patch_word(p, 1), k));
+    neph = static_cast<int64_t>(writelane64(static_cast<uint64_t>(neph), w.patch_word(p, 2), k));
+    nport = writelane64(nport, w.patch_word(p, 3), k);
+    nleft = writelane(nleft, w.dirty_left(p), k);
+  }
+}
 // s_ff1_i32_b64: the lowest set bit of a scalar mask, -1 when it is zero (the
 // compiler's ctz of a maybe-zero value adds a compare and a select)
 __device__ __forceinline__ int ff1(uint64_t x) {
@@ -1309,7 +1400,7 @@ constexpr int kCoopPods = 64;
 struct CoopArea {
   int32_t cmd, n, sw, pad;                 // cmd 0: a resolution request of n pods from word sw; 1: exit
   uint64_t r01[kCoopPods], r23[kCoopPods];  // the pods' row offsets
-  int64_t rq[kCoopPods][3];                 // ... requests (K0-less corrections)
+  uint32_t fm[kCoopPods];                   // ... fit masks of the changed nodes (K0-less corrections: fix_dirty)
   int32_t op[kCoopPods][8];                 // ... class programs (head-only S rows)
   uint32_t best[kCoopPods];                 // lowest chunk found by any wave so far (skips higher ones)
   uint32_t rk[kCoopWaves][kCoopPods];       // per wave: first chunk of its share with a non-zero word (~0: none)
@@ -1321,11 +1412,13 @@ struct CoopArea {
 // request's first chunk, each for every pod not resolved by a lower chunk
 // yet, Q pods' loads in flight per round trip (as the chain's own resolve).
 template <bool HO>
-__device__ __forceinline__ void coop_scan(const DevWorkload& w, CoopArea& A, int h) {
+__device__ __forceinline__ void coop_scan(const K2W& w, CoopArea& A, int h) {
   const int lane = threadIdx.x & 63;
   const int n = __builtin_amdgcn_readfirstlane(A.n), sw = __builtin_amdgcn_readfirstlane(A.sw);
-  const int Wp = w.Wp;
-  const uint64_t* __restrict__ tab = w.S;
+  const int Wp = w.Wp();
+  const uint64_t* __restrict__ tab = w.S();
+  const uint64_t* __restrict__ atoms = w.atoms();
+  const bool k0_skip = w.k0_skip() != 0;
   if (lane < n) A.rk[h][lane] = 0xffffffffu;
   const int cb0 = (sw >> 6) << 6;
   const int nch = (Wp - cb0 + 63) >> 6;
@@ -1365,7 +1458,7 @@ __device__ __forceinline__ void coop_scan(const DevWorkload& w, CoopArea& A, int
         if constexpr (HO) {
 #pragma unroll
           for (int u = 0; u < 8; ++u)
-            x[q][u] = op[q][u] >= 0 ? w.atoms[static_cast<size_t>(op[q][u] >> 2) * Wp + wi] : 0ull;
+            x[q][u] = op[q][u] >= 0 ? atoms[static_cast<size_t>(op[q][u] >> 2) * Wp + wi] : 0ull;
           x[q][8] = tab[static_cast<uint32_t>(a01[q] >> 32) + wi];
           x[q][9] = tab[static_cast<uint32_t>(a23[q]) + wi];
           x[q][10] = tab[static_cast<uint32_t>(a23[q] >> 32) + wi];
@@ -1391,10 +1484,7 @@ __device__ __forceinline__ void coop_scan(const DevWorkload& w, CoopArea& A, int
           sw0 = x[q][0];
           f = x[q][0] & x[q][1] & x[q][2] & x[q][3];
         }
-        if (w.k0_skip) {
-          const int64_t rc = A.rq[j][0], rm = A.rq[j][1], re = A.rq[j][2];
-          f = fix_dirty(w, f, sw0, word, rc, rm, re, (rc | rm | re) == 0);
-        }
+        if (k0_skip) f = fix_dirty(w, f, sw0, word, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(A.fm[j])));
         const uint64_t m = ballot(wv && f != 0) & vw;
         if (m == 0) continue;
         found |= 1ull << j;
@@ -1413,11 +1503,12 @@ __device__ __forceinline__ void coop_scan(const DevWorkload& w, CoopArea& A, int
 // A helper wave of a cooperative block: scans its share of every request the
 // chain wave posts until the chain posts the exit (the same number of block
 // barriers on every wave).
-__device__ __forceinline__ void coop_helper(const DevWorkload& w, CoopArea& A, int h) {
+__device__ __forceinline__ void coop_helper(const K2W& w, CoopArea& A, int h) {
+  const bool head_only = w.s_head_only() != 0;
   for (;;) {
     __syncthreads();
     if (__hip_atomic_load(&A.cmd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) break;
-    if (w.s_head_only) coop_scan<true>(w, A, h);
+    if (head_only) coop_scan<true>(w, A, h);
     else coop_scan<false>(w, A, h);
     __syncthreads();
   }
@@ -1443,15 +1534,17 @@ __device__ __forceinline__ int wave_sum(int v) {
 // COOP: the candidate's block cooperates on far resolutions (CoopArea A:
 // this wave is the chain, the block's other waves scan with it).
 template <int G, bool PROF, bool WIDE = false, bool XT = false, bool COOP = false>
-__device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __restrict__ F, const int p0,
+__device__ __forceinline__ void k2_node_order(const K2W& w, uint64_t* __restrict__ F, const int p0,
                                               const int np, int& status, K2Stats& st, uint32_t& nbytes,
                                               int (&mapv)[kMapG], const int ebase = -1, const int erow0_in = -2,
                                               const int erow1_in = -2, CoopArea* A = nullptr) {
   static_assert(64 * G * kNHS * 8 <= sizeof(K2Lds), "node-order LDS exceeds the wave's K2 region");
   static_assert(G <= kMapG, "a mapping register per pod group");
   const int lane = threadIdx.x & 63;
-  const int Wp = w.Wp;
-  const uint64_t* __restrict__ tab = w.S;
+  const int Wp = w.Wp();
+  const uint64_t* __restrict__ tab = w.S();
+  const bool k0_skip = w.k0_skip() != 0, head_only = w.s_head_only() != 0;
+  const int n_dirty = w.n_dirty();
   int64_t rc[G], rm[G], re[G];
   uint64_t pm[G], ps[G], r01[G], r23[G], fmask[G], act[G];
   int fbase[G];  // first word of the 64-word chunk fmask describes (rows wider than 64 words)
@@ -1461,13 +1554,15 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
   bool zero[G];
   int ptr[G], node[G];
   int dead = np;  // first pod with no feasible spot node left
+  const uint64_t swap_mask = w.swap_mask();
+  const uint32_t s_empty_off = w.s_empty_off();
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    const uint64_t* pr = w.pod_rec + static_cast<size_t>(p0 + min(64 * g + lane, np - 1)) * kRecU64;
+    const uint64_t* pr = w.pod_rec() + static_cast<size_t>(p0 + min(64 * g + lane, np - 1)) * kRecU64;
     rc[g] = static_cast<int64_t>(pr[0]);
     rm[g] = static_cast<int64_t>(pr[1]);
     re[g] = static_cast<int64_t>(pr[2]);
-    pm[g] = swap_pairs(pr[3], w.swap_mask);  // the state bits the pod conflicts with
+    pm[g] = swap_pairs(pr[3], swap_mask);  // the state bits the pod conflicts with
     ps[g] = pr[3];                            // ... and those it sets
     r01[g] = pr[4];
     r23[g] = pr[5];
@@ -1479,22 +1574,23 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
     cur[g] = 0;
     ptr[g] = INT_MAX;
     node[g] = -1;
-    const uint64_t e = ballot(64 * g + lane < np && static_cast<uint32_t>(r01[g]) == w.s_empty_off);
+    const uint64_t e = ballot(64 * g + lane < np && static_cast<uint32_t>(r01[g]) == s_empty_off);
     if (e != 0) dead = min(dead, 64 * g + __builtin_ctzll(e));
   }
+  if (k0_skip) w.fetch_patches();  // in flight with the pod records
   // XT: the pods' extension records and the slots' node_scal rows
   XVals<int64_t> xv[G];
   int erow0 = -1, erow1 = -1;
   if constexpr (XT) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const uint64_t* er = w.pod_ext + static_cast<size_t>(ebase + min(64 * g + lane, np - 1)) * kDevExtU64;
+      const uint64_t* er = w.pod_ext() + static_cast<size_t>(ebase + min(64 * g + lane, np - 1)) * kDevExtU64;
       xv[g] = {static_cast<int64_t>(er[0]), static_cast<int64_t>(er[1]), static_cast<int64_t>(er[2]),
                static_cast<int64_t>(er[3]), static_cast<int64_t>(er[4]), static_cast<int64_t>(er[5]),
                static_cast<int64_t>(er[6])};
     }
     if (erow0_in == -2) {
-      const uint64_t erow = w.pod_ext[static_cast<size_t>(ebase) * kDevExtU64 + 7];
+      const uint64_t erow = w.pod_ext()[static_cast<size_t>(ebase) * kDevExtU64 + 7];
       erow0 = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(static_cast<uint32_t>(erow)));
       erow1 = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(erow >> 32));
     } else {
@@ -1561,7 +1657,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
                  static_cast<uint32_t>(v.a1)};
       }
     }
-    narrow = w.k2_narrow && ballot(!ok) == 0;
+    narrow = w.k2_narrow() && ballot(!ok) == 0;
   }
   // some pod asks for ephemeral storage (E) / sets or meets state bits (O):
   // without them those checks are uniform over the visit and never change
@@ -1586,7 +1682,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
       bool all = true;
 #pragma unroll
       for (int g = 0; g < G; ++g) all = all && ballot(64 * g + lane < np && !(((ps[g] & pm[g]) >> b) & 1)) == 0;
-      X = all && w.k2_excl;
+      X = all && w.k2_excl();
     }
   }
   // node records of window 0 (spot nodes [0, 64)), where first fit usually
@@ -1599,19 +1695,18 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
   auto load_scal = [&](int W) {
     if constexpr (XT) {
       const size_t n = static_cast<size_t>(64 * W + lane);
-      ns0 = erow0 >= 0 ? w.node_scal[static_cast<size_t>(erow0) * w.n_pad + n] : 0;
-      ns1 = erow1 >= 0 ? w.node_scal[static_cast<size_t>(erow1) * w.n_pad + n] : 0;
+      ns0 = erow0 >= 0 ? w.node_scal()[static_cast<size_t>(erow0) * w.n_pad() + n] : 0;
+      ns1 = erow1 >= 0 ? w.node_scal()[static_cast<size_t>(erow1) * w.n_pad() + n] : 0;
       nbytes += 64u * 16u;
     }
   };
   if (dead > 0) {
-    const uint64_t* nr = w.node_rec + static_cast<size_t>(lane) * 8;
+    const uint64_t* nr = w.node_rec() + static_cast<size_t>(lane) * 8;
     ncpu = static_cast<int64_t>(nr[0]);
     nmem = static_cast<int64_t>(nr[1]);
     neph = static_cast<int64_t>(nr[2]);
     nport = nr[3];
-    nleft = static_cast<int>(static_cast<int64_t>(nr[4]));
-    if (w.k0_skip) window_patch(w, 0, lane, ncpu, nmem, neph, nport, nleft);
+    nleft = static_cast<int>(static_cast<int64_t>(nr[4]));  // (K0-less runs: patched after the F heads, below)
     load_scal(0);
     wcur = 0;
     nbytes += 64u * 40u;
@@ -1625,12 +1720,12 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
   // (pods from the first dead one on are never scanned: a candidate whose
   // first pod fits no node -- C4: 2,254 of 15,000 -- loads none)
   int32_t* PG = reinterpret_cast<int32_t*>(F + 64 * G * kNHS);
-  if (w.s_head_only && dead > 0) {
+  if (head_only && dead > 0) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       if (64 * g >= dead) break;  // wave-uniform
       const uint32_t cls = static_cast<uint32_t>(r01[g]) / static_cast<uint32_t>(Wp);
-      const int4* p8 = reinterpret_cast<const int4*>(w.cls_prog8 + static_cast<size_t>(cls) * 8);
+      const int4* p8 = reinterpret_cast<const int4*>(w.cls_prog8() + static_cast<size_t>(cls) * 8);
       const int4 a = p8[0], b = p8[1];
       int4* dst = reinterpret_cast<int4*>(PG + (64 * g + lane) * 8);
       dst[0] = a;
@@ -1646,22 +1741,24 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
 
   // head words holding a node changed since the tables were written (K0-less
   // runs), and per pod (its lane) whether it fits each changed node: bit p for
-  // node patch p (at most 16)
+  // node patch p (at most 16).  The nodes and their free values come from the
+  // wave's table (K2W), the compares joined without a branch; the masks serve
+  // the F heads, the far resolutions and the pointer moves (fix_dirty).
   uint32_t dirty_head = 0;
   uint32_t dfit[G];
-  for (int p = 0; p < w.n_dirty; ++p) {  // kernel arguments
-    const int wd0 = w.dirty_node[p] >> 6;
+  for (int p = 0; p < n_dirty; ++p) {
+    const int wd0 = w.dirty_node(p) >> 6;
     dirty_head |= wd0 < kNH ? 1u << wd0 : 0u;
   }
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    dfit[g] = 0;
-    if (dirty_head != 0)
-      for (int p = 0; p < w.n_dirty; ++p) {
-        const bool fits = zero[g] || (w.dirty_free[p][0] >= rc[g] && w.dirty_free[p][1] >= rm[g] &&
-                                      w.dirty_free[p][2] >= re[g]);
-        dfit[g] |= fits ? 1u << p : 0u;
-      }
+  for (int g = 0; g < G; ++g) dfit[g] = 0;
+  for (int p = 0; p < n_dirty; ++p) {
+    const int64_t f0 = w.dirty_free(p, 0), f1 = w.dirty_free(p, 1), f2 = w.dirty_free(p, 2);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const bool fits = zero[g] | ((f0 >= rc[g]) & (f1 >= rm[g]) & (f2 >= re[g]));
+      dfit[g] |= fits ? 1u << p : 0u;
+    }
   }
   // F heads of pods [0, dead): lanes = kPW pods x kNH words, kPB such batches
   // per step with all their loads in flight together (one memory round trip
@@ -1680,6 +1777,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
         int kk[kPB];
         uint32_t fm[kPB];  // the pod's fit mask of the changed nodes (K0-less runs), with its row offsets
         const uint64_t cyc_ld0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
+        if (PROF && st.cyc_fh == 0) st.cyc_fh = cyc_ld0;
 #pragma unroll
         for (int h = 0; h < kPB; ++h) {
           kk[h] = b0 + kPW * h + sub;
@@ -1707,12 +1805,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
           if (b0 + kPW * h >= lim) continue;  // wave-uniform
           uint64_t f = (wv && kk[h] < np) ? x[h][0] & x[h][1] & x[h][2] & x[h][3] : 0ull;
           if (dirty_head != 0) {  // the changed nodes' bits, from the pod's fit mask
-            for (int p = 0; p < w.n_dirty; ++p) {
-              const int n = w.dirty_node[p];
-              if ((n >> 6) != wd) continue;
-              const uint64_t bit = 1ull << (n & 63);
-              f = (fm[h] >> p) & 1 ? (f | (x[h][0] & bit)) : (f & ~bit);
-            }
+            f = fix_dirty(w, f, x[h][0], wd, fm[h]);
             f = (wv && kk[h] < np) ? f : 0ull;
           }
           if (kk[h] < np) F[kk[h] * kNHS + wd] = f;
@@ -1756,6 +1849,8 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
     cyc_t = t;
   }
 
+  // K0-less runs: window 0's changed nodes, now that its records have long arrived
+  if (k0_skip && wcur == 0) window_patch(w, 0, ncpu, nmem, neph, nport, nleft);
   int visits = 0, placements = 0, windows = wcur + 1;
   while (any != 0) {
     int mine = INT_MAX;
@@ -1793,7 +1888,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
           while (pend != 0) {
             int js[Q];
             uint64_t a01[Q], a23[Q];
-            int64_t qr[Q][3];
+            uint32_t qf[Q];  // the pod's fit mask of the changed nodes
             int op[Q][8];
             uint32_t nops[Q];
 #pragma unroll
@@ -1803,9 +1898,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
               const int j = js[q] < 0 ? 0 : js[q];
               a01[q] = readlane64(r01[g], j);
               a23[q] = readlane64(r23[g], j);
-              qr[q][0] = static_cast<int64_t>(readlane64(static_cast<uint64_t>(rc[g]), j));
-              qr[q][1] = static_cast<int64_t>(readlane64(static_cast<uint64_t>(rm[g]), j));
-              qr[q][2] = static_cast<int64_t>(readlane64(static_cast<uint64_t>(re[g]), j));
+              qf[q] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(dfit[g]), j));
               nops[q] = 0;
               if constexpr (HO) {  // the pod's class program (LDS, broadcast)
 #pragma unroll
@@ -1831,7 +1924,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
                 if constexpr (HO) {
 #pragma unroll
                   for (int u = 0; u < 8; ++u)
-                    x[q][u] = op[q][u] >= 0 ? w.atoms[static_cast<size_t>(op[q][u] >> 2) * Wp + wi] : 0ull;
+                    x[q][u] = op[q][u] >= 0 ? w.atoms()[static_cast<size_t>(op[q][u] >> 2) * Wp + wi] : 0ull;
                   x[q][8] = tab[static_cast<uint32_t>(a01[q] >> 32) + wi];
                   x[q][9] = tab[static_cast<uint32_t>(a23[q]) + wi];
                   x[q][10] = tab[static_cast<uint32_t>(a23[q] >> 32) + wi];
@@ -1861,8 +1954,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
                   sw0 = x[q][0];
                   f = x[q][0] & x[q][1] & x[q][2] & x[q][3];
                 }
-                if (w.k0_skip)
-                  f = fix_dirty(w, f, sw0, word, qr[q][0], qr[q][1], qr[q][2], (qr[q][0] | qr[q][1] | qr[q][2]) == 0);
+                if (k0_skip) f = fix_dirty(w, f, sw0, word, qf[q]);
                 f = wv ? f : 0ull;
                 const uint64_t m = ballot(f != 0);
                 // algorithmic bytes: the words a sequential scan reads, up to the
@@ -1907,10 +1999,8 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
           if (mine) {
             A->r01[slot] = r01[g];
             A->r23[slot] = r23[g];
-            A->rq[slot][0] = rc[g];
-            A->rq[slot][1] = rm[g];
-            A->rq[slot][2] = re[g];
-            if (w.s_head_only)
+            A->fm[slot] = dfit[g];
+            if (head_only)
 #pragma unroll
               for (int u = 0; u < 8; ++u) {
                 const int o = PG[(64 * g + lane) * 8 + u];
@@ -1925,7 +2015,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
             A->sw = sw;
           }
           __syncthreads();  // the request is posted: every wave scans its share
-          if (w.s_head_only) coop_scan<true>(w, *A, 0);
+          if (head_only) coop_scan<true>(w, *A, 0);
           else coop_scan<false>(w, *A, 0);
           __syncthreads();  // every share scanned
           if (PROF) st.cyc_res += static_cast<uint64_t>((Wp - ((sw >> 6) << 6) + 64 * kCoopWaves - 1) /
@@ -1956,7 +2046,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
             }
             ptr[g] = nx;
             unres[g] = false;
-            bytes = static_cast<uint32_t>(words) * (w.s_head_only ? 8u * (static_cast<uint32_t>(nops) + 3u) : 32u);
+            bytes = static_cast<uint32_t>(words) * (head_only ? 8u * (static_cast<uint32_t>(nops) + 3u) : 32u);
           }
           nbytes += static_cast<uint32_t>(wave_sum(static_cast<int>(bytes)));
           const uint64_t gone = ballot(mine && ptr[g] == INT_MAX);
@@ -1968,7 +2058,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
       // variant's resolution slower, 21-28k cycles against 17.5k)
       constexpr int kResQ = 4;
       if constexpr (COOP) coop_resolve();
-      else if (w.s_head_only) resolve(std::integral_constant<int, 2>{}, std::true_type{});
+      else if (head_only) resolve(std::integral_constant<int, 2>{}, std::true_type{});
       else resolve(std::integral_constant<int, kResQ>{}, std::false_type{});
       if (PROF) st.cyc_res += __builtin_amdgcn_s_memtime() - cyc_r0;
       any = 0;
@@ -1983,13 +2073,13 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
     const int W = n >> 6;
     if (W != wcur) {  // wave-uniform
       const uint64_t cyc_w0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
-      const uint64_t* nr = w.node_rec + static_cast<size_t>(W * 64 + lane) * 8;
+      const uint64_t* nr = w.node_rec() + static_cast<size_t>(W * 64 + lane) * 8;
       ncpu = static_cast<int64_t>(nr[0]);
       nmem = static_cast<int64_t>(nr[1]);
       neph = static_cast<int64_t>(nr[2]);
       nport = nr[3];
       nleft = static_cast<int>(static_cast<int64_t>(nr[4]));
-      if (w.k0_skip) window_patch(w, W, lane, ncpu, nmem, neph, nport, nleft);
+      if (k0_skip) window_patch(w, W, ncpu, nmem, neph, nport, nleft);
       load_scal(W);
       wcur = W;
       ++windows;
@@ -2032,7 +2122,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
         if (todo != 0) {
           const int kmax = dead - 64 * g;  // pods above the first dead one are irrelevant
 #define SR_PW(e_, o_)                                                                                             \
-  place_window<e_, o_>(todo, kmax, W, lane, rc[g], rm[g], re[g], pm[g], cur[g], zm[g], w.swap_mask, emask, ncpu, \
+  place_window<e_, o_>(todo, kmax, W, lane, rc[g], rm[g], re[g], pm[g], cur[g], zm[g], swap_mask, emask, ncpu, \
                        nmem, neph, nport, nleft, node[g])
 #define SR_PW32(e_, o_)                                                                                           \
   place_window32<e_, o_>(todo, kmax, W, lane, nc[g], nm[g], ne[g], pm[g], ps[g], cur[g], c32, m32, e32, \
@@ -2041,7 +2131,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
   place_window32<e_, true, true>(todo, kmax, W, lane, nc[g], nm[g], ne[g], pm[g], ps[g], cur[g], c32, m32, e32, \
                                  nport, nleft, node[g])
 #define SR_PWX(e_, o_)                                                                                          \
-  place_window_x<e_, o_>(todo, kmax, W, lane, rc[g], rm[g], re[g], xv[g], pm[g], cur[g], zm[g], w.swap_mask, emask, \
+  place_window_x<e_, o_>(todo, kmax, W, lane, rc[g], rm[g], re[g], xv[g], pm[g], cur[g], zm[g], swap_mask, emask, \
                          ncpu, nmem, neph, nport, nleft, ns0, ns1, node[g])
 #define SR_PW32XT(e_, o_)                                                                                       \
   place_window32_x<e_, o_>(todo, kmax, W, lane, nc[g], nm[g], ne[g], nx[g], pm[g], ps[g], cur[g], c32, m32, e32, \
@@ -2098,12 +2188,12 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
           const uint64_t rem = lw >= 63 ? 0ull : fmask[g] & (~0ull << (lw + 1));
           if (rem != 0) {
             const int w2 = fbase[g] + __builtin_ctzll(rem);
-            cur[g] = w.s_head_only ? f_word_prog(w, tab, PG + (64 * g + lane) * 8, r01[g], r23[g], w2)
-                                   : f_word_far(tab, r01[g], r23[g], w2);
-            if (w.k0_skip) {  // the S word again for the changed nodes' bits
-              const uint64_t sw0 = w.s_head_only ? f_word_prog_s(w, PG + (64 * g + lane) * 8, w2)
-                                                 : tab[static_cast<uint32_t>(r01[g]) + w2];
-              cur[g] = fix_dirty(w, cur[g], sw0, w2, rc[g], rm[g], re[g], zero[g]);
+            cur[g] = head_only ? f_word_prog(w, tab, PG + (64 * g + lane) * 8, r01[g], r23[g], w2)
+                               : f_word_far(tab, r01[g], r23[g], w2);
+            if (k0_skip) {  // the S word again for the changed nodes' bits
+              const uint64_t sw0 = head_only ? f_word_prog_s(w, PG + (64 * g + lane) * 8, w2)
+                                             : tab[static_cast<uint32_t>(r01[g]) + w2];
+              cur[g] = fix_dirty(w, cur[g], sw0, w2, dfit[g]);
             }
             nx = w2 * 64 + __builtin_ctzll(cur[g]);
             far_word = true;
@@ -2141,7 +2231,7 @@ __device__ __forceinline__ void k2_node_order(const DevWorkload& w, uint64_t* __
   for (int g = 0; g < G; ++g) {
     const int k = 64 * g + lane;
     mapv[g] = k < dead ? node[g] : -1;  // (k2_finish: the winner's mapping without a read-back)
-    if (k < np) w.out_node[p0 + k] = mapv[g];
+    if (k < np) w.out_node()[p0 + k] = mapv[g];
   }
 }
 
@@ -2561,11 +2651,11 @@ struct K2Entry {
   uint64_t t_start, c_start, t_list;
 };
 template <bool PROF>
-__device__ __forceinline__ K2Entry k2_entry(const DevWorkload& w, const int4* __restrict__ list, int li) {
+__device__ __forceinline__ K2Entry k2_entry(const K2W& w, const int4* __restrict__ list, int li) {
   K2Entry x;
   x.t_start = PROF ? __builtin_amdgcn_s_memrealtime() : 0;
-  x.c_start = PROF || w.out_cycles ? __builtin_amdgcn_s_memtime() : 0;
-  const int4 e = li < w.n_list_head ? w.list_head[li] : list[li];  // the head: with the kernel arguments
+  x.c_start = __builtin_amdgcn_s_memtime();
+  const int4 e = li < w.n_list_head() ? w.k.list_head[li] : list[li];  // the head: with the kernel arguments
   x.ci = __builtin_amdgcn_readfirstlane(e.x);
   x.p0 = __builtin_amdgcn_readfirstlane(e.y);
   x.np = __builtin_amdgcn_readfirstlane(e.z) - x.p0;  // >= 1: empty candidates never reach the device
@@ -2600,84 +2690,97 @@ __device__ __forceinline__ void k2_skipped(const DevWorkload& w, int ci) {
 // The candidate's mapping, where the wave still holds it: `mapv` when in_regs
 // (node order: pod 64 * g + lane in mapv[g]) or `lmap` (pod order: the wave's
 // L.omap).  The domain path hands over neither.
+// Every pointer and the run's tag come from the wave's header (K2W): the
+// stores go out one after the other, none behind a load of its address.
 template <bool PROF>
-__device__ __forceinline__ void k2_finish(const DevWorkload& w, const K2Entry& x, int status, int wide,
+__device__ __forceinline__ void k2_finish(const K2W& w, const K2Entry& x, int status, int wide,
                                           uint32_t nbytes, const K2Stats& st, const int (&mapv)[kMapG],
                                           const bool in_regs = true, const int32_t* lmap = nullptr) {
+  const uint64_t cyc_fin = PROF ? __builtin_amdgcn_s_memtime() : 0;
   const int lane = threadIdx.x & 63;
   const int ci = x.ci, p0 = x.p0, np = x.np;
   int best = 0;  // lane 0: this candidate is the first drainable one so far
-  if (lane == 0 && ci == 0) k2_once(w);
+  unsigned long long* const dm = reinterpret_cast<unsigned long long*>(w.d_min());
+  uint64_t* const res_stat = w.res_stat();
+  if (lane == 0 && ci == 0) k2_once(w.k);
   if (lane == 0) {
-    w.out_status[ci] = status;
-    w.out_bytes[ci] = nbytes;
-    if (w.out_cycles)
-      w.out_cycles[ci] = static_cast<uint32_t>(min(__builtin_amdgcn_s_memtime() - x.c_start, 0xffffffffull));
+    uint32_t* const out_cycles = w.out_cycles();
+    w.out_status()[ci] = status;
+    w.out_bytes()[ci] = nbytes;
+    if (out_cycles) out_cycles[ci] = static_cast<uint32_t>(min(__builtin_amdgcn_s_memtime() - x.c_start, 0xffffffffull));
     // packed (global candidate << 32 | local candidate): min = first drainable
     if (status < 0) {
       const unsigned long long key = (static_cast<unsigned long long>(x.g) << 32) | static_cast<unsigned>(ci);
-      best = key < atomicMin(reinterpret_cast<unsigned long long*>(w.d_min), key);
-    }
-    if (PROF) {
-      uint64_t* pr = w.prof + static_cast<size_t>(ci) * 16;
-      pr[0] = x.t_start;
-      pr[1] = x.t_list;  // the work-list entry has arrived
-      pr[2] = __builtin_amdgcn_s_memrealtime();
-      pr[3] = __builtin_amdgcn_s_memtime() - x.c_start;
-      pr[4] = static_cast<uint64_t>(status >= 0 ? status + 1 : np);
-      pr[5] = static_cast<uint64_t>(wide);
-      pr[6] = st.n_spec_miss;
-      pr[7] = static_cast<uint64_t>(st.n_min) | (static_cast<uint64_t>(st.n_far) << 32);
-      pr[8] = st.cyc_a;
-      pr[9] = st.cyc_b;
-      pr[10] = st.cyc_c;
-      pr[11] = st.cyc_d;
-      if (wide == 2) {  // node order (sections of a wave stay far below 2^32 cycles: the high halves carry the split)
-        pr[8] |= static_cast<uint64_t>(st.cyc_a_ld) << 32;
-        pr[10] |= static_cast<uint64_t>(st.n_res_pods) << 32 | static_cast<uint64_t>(st.n_res) << 48;
-        pr[11] |= static_cast<uint64_t>(st.cyc_res_ld) << 32;
-        pr[12] = st.cyc_res;
-        pr[13] = st.cyc_win;
-        pr[14] = st.cyc_rec - x.c_start;
-        pr[15] = st.narrow | (status < 0 ? 16u : 0u);  // (16: the candidate is drainable)
-      }
+      best = key < atomicMin(dm, key);
     }
   }
-  if (w.res_stat) {
+  auto profile = [&]() {  // profile builds, lane 0, after the wave's last store
+    const uint64_t cyc_end = __builtin_amdgcn_s_memtime();
+    uint64_t* pr = w.prof() + static_cast<size_t>(ci) * 16;
+    pr[0] = x.t_start;
+    pr[1] = x.t_list;  // the work-list entry has arrived
+    pr[2] = __builtin_amdgcn_s_memrealtime();
+    pr[3] = __builtin_amdgcn_s_memtime() - x.c_start;
+    pr[4] = static_cast<uint64_t>(status >= 0 ? status + 1 : np);
+    pr[5] = static_cast<uint64_t>(wide);
+    pr[6] = st.n_spec_miss;
+    pr[7] = static_cast<uint64_t>(st.n_min) | (static_cast<uint64_t>(st.n_far) << 32);
+    pr[8] = st.cyc_a;
+    pr[9] = st.cyc_b;
+    pr[10] = st.cyc_c;
+    pr[11] = st.cyc_d;
+    if (wide == 2) {  // node order (sections of a wave stay far below 2^32 cycles: the high halves carry the split)
+      pr[8] |= static_cast<uint64_t>(st.cyc_a_ld) << 32;
+      pr[10] |= static_cast<uint64_t>(st.n_res_pods) << 32 | static_cast<uint64_t>(st.n_res) << 48;
+      pr[11] |= static_cast<uint64_t>(st.cyc_res_ld) << 32;
+      pr[12] = st.cyc_res;
+      pr[13] = st.cyc_win;
+      pr[14] = st.cyc_rec - x.c_start;
+      pr[15] = st.narrow | (status < 0 ? 16u : 0u);  // (16: the candidate is drainable)
+      // records arrived -> first F-head load issued; entry of k2_finish -> last store issued
+      pr[9] |= static_cast<uint64_t>(st.cyc_fh ? static_cast<uint32_t>(st.cyc_fh - st.cyc_rec) : 0u) << 32;
+      pr[13] |= static_cast<uint64_t>(static_cast<uint32_t>(cyc_end - cyc_fin)) << 32;
+    }
+  };
+  if (res_stat) {
     // Single rank: the host walks res_stat in candidate order and stops at the
     // first drainable candidate, whose mapping is in res_map -- its wave was
     // necessarily the first drainable one so far when it finished -- so the
     // result is in host memory as soon as the candidates up to the winner are
     // planned, not when the whole grid is.  Every word carries the run's tag
     // and is accepted on its own: no store waits for another.
-    const uint64_t tag = static_cast<uint64_t>(w.seq) << 32;
+    const uint64_t tag = static_cast<uint64_t>(w.seq()) << 32;
+    uint64_t* const res_map = w.res_map();
+    const bool map_regs = w.k2_map_regs() != 0;
     if (__builtin_amdgcn_readfirstlane(best)) {
       // a first drainable candidate placed every pod: the mapping is whole in
       // the wave's registers or LDS, and goes out without waiting for the
       // out_node stores (SR_K2_MAP_REGS=0: read back from out_node, as the
       // domain path does)
-      if (in_regs && w.k2_map_regs) {
+      if (in_regs && map_regs) {
 #pragma unroll
         for (int g = 0; g < kMapG; ++g)
           if (64 * g + lane < np)
-            __hip_atomic_store(w.res_map + p0 + 64 * g + lane, tag | static_cast<uint32_t>(mapv[g]), __ATOMIC_RELAXED,
+            __hip_atomic_store(res_map + p0 + 64 * g + lane, tag | static_cast<uint32_t>(mapv[g]), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_SYSTEM);
-      } else if (lmap && w.k2_map_regs) {
+      } else if (lmap && map_regs) {
         for (int q = lane; q < np; q += 64)
-          __hip_atomic_store(w.res_map + p0 + q, tag | static_cast<uint32_t>(lmap[q]), __ATOMIC_RELAXED,
+          __hip_atomic_store(res_map + p0 + q, tag | static_cast<uint32_t>(lmap[q]), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_SYSTEM);
       } else {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's out_node stores, then read back
+        const int32_t* out_node = w.out_node();
         for (int q = lane; q < np; q += 64)
-          __hip_atomic_store(w.res_map + p0 + q,
-                             tag | static_cast<uint32_t>(__hip_atomic_load(w.out_node + p0 + q, __ATOMIC_RELAXED,
+          __hip_atomic_store(res_map + p0 + q,
+                             tag | static_cast<uint32_t>(__hip_atomic_load(out_node + p0 + q, __ATOMIC_RELAXED,
                                                                            __HIP_MEMORY_SCOPE_AGENT)),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
     if (lane == 0)
-      __hip_atomic_store(w.res_stat + ci, tag | (status < 0 ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(res_stat + ci, tag | (status < 0 ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  if (PROF && lane == 0) profile();
 }
 
 template <int CH, bool PROF>
@@ -2689,7 +2792,8 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   const int wave = threadIdx.x >> 6;
   const int li = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * (blockDim.x >> 6)) + wave);
   if (li >= n_list) return;
-  const K2Entry x = k2_entry<PROF>(w, list, li);
+  const K2W hw(w);  // the work-list entry, the node-order path and k2_finish: the wave header
+  const K2Entry x = k2_entry<PROF>(hw, list, li);
   if (x.g <= w.cand_floor) {  // (a sequence round: judged before)
     k2_skipped(w, x.ci);
     return;
@@ -2716,9 +2820,9 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   } else if (node_order && ebase >= 0) {  // extension records, node order (place_window_x); writes out_node
     uint64_t* F = reinterpret_cast<uint64_t*>(&L);
     wide = 2;
-    if (np <= 64) k2_node_order<1, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
-    else if (np <= 128) k2_node_order<2, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
-    else k2_node_order<4, PROF, false, true>(w, F, p0, np, status, st, nbytes, mapv, ebase);
+    if (np <= 64) k2_node_order<1, PROF, false, true>(hw, F, p0, np, status, st, nbytes, mapv, ebase);
+    else if (np <= 128) k2_node_order<2, PROF, false, true>(hw, F, p0, np, status, st, nbytes, mapv, ebase);
+    else k2_node_order<4, PROF, false, true>(hw, F, p0, np, status, st, nbytes, mapv, ebase);
     in_regs = true;
   } else if (ebase >= 0) {  // extension records, pod order (SR_K2_MODE=1) with the extended running state
     int placed = k2_run<1, CH, PROF, true>(w, L, p0, np, status, st, nbytes, ebase);
@@ -2729,9 +2833,9 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
   } else if (node_order) {  // writes out_node itself
     uint64_t* F = reinterpret_cast<uint64_t*>(&L);
     wide = 2;
-    if (np <= 64) k2_node_order<1, PROF>(w, F, p0, np, status, st, nbytes, mapv);
-    else if (np <= 128) k2_node_order<2, PROF>(w, F, p0, np, status, st, nbytes, mapv);
-    else k2_node_order<4, PROF>(w, F, p0, np, status, st, nbytes, mapv);
+    if (np <= 64) k2_node_order<1, PROF>(hw, F, p0, np, status, st, nbytes, mapv);
+    else if (np <= 128) k2_node_order<2, PROF>(hw, F, p0, np, status, st, nbytes, mapv);
+    else k2_node_order<4, PROF>(hw, F, p0, np, status, st, nbytes, mapv);
     in_regs = true;
   } else {
     int placed = k2_run<1, CH, PROF>(w, L, p0, np, status, st, nbytes);
@@ -2740,7 +2844,7 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
     for (int i = lane; i < np; i += 64) w.out_node[p0 + i] = i < placed ? L.omap[i] : -1;
     in_lds = true;
   }
-  k2_finish<PROF>(w, x, status, wide, nbytes, st, mapv, in_regs, in_lds ? L.omap : nullptr);
+  k2_finish<PROF>(hw, x, status, wide, nbytes, st, mapv, in_regs, in_lds ? L.omap : nullptr);
 }
 
 // K2 when every candidate of the launch takes node order (no domain-path
@@ -2752,29 +2856,30 @@ __global__ __launch_bounds__(256) void k2_place(DevWorkload w_arg, const int4* _
 // launch without them keeps the lean kernel).
 template <int GMAX, bool PROF, bool WIDE = false, bool XT = false>
 __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __restrict__ list, int n_list) {
-  // the workload read in place from the kernel-argument segment (w_arg is its
-  // first argument): each field is a scalar load where it is used, instead of
-  // values held (or spilled to scratch) across the kernel
-  const DevWorkload& w = *(const DevWorkload*)__builtin_amdgcn_kernarg_segment_ptr();
+  // the workload in place in the kernel-argument segment (w_arg is its first
+  // argument): the wave's header and changed-node table are fetched from it
+  // here, once (K2W); `wk` serves what a wave reads once at its entry
+  const DevWorkload& wk = *(const DevWorkload*)__builtin_amdgcn_kernarg_segment_ptr();
   (void)w_arg;
+  const K2W w(wk);
   extern __shared__ __attribute__((aligned(16))) uint64_t k2_lds[];
   const int wave = threadIdx.x >> 6;
-  const size_t region = 64 * GMAX * kNHS + (w.s_head_only ? 64 * GMAX * 4 : 0);  // LDS words per wave
+  const size_t region = 64 * GMAX * kNHS + (w.s_head_only() ? 64 * GMAX * 4 : 0);  // LDS words per wave
   // the first n_coop blocks: one candidate each (the list's costliest), wave 0
   // its chain, the other waves scanning with it (launches of kCoopWaves waves
   // per block without extension records)
-  const int nco = XT ? 0 : w.n_coop;
+  const int nco = XT ? 0 : w.n_coop();
   if constexpr (!XT) {
     static_assert(sizeof(CoopArea) <= (kCoopWaves - 1) * 64 * kNHS * 8, "the cooperative area fits the helpers' LDS");
     if (static_cast<int>(blockIdx.x) < nco) {
       // a sequence round: every wave of the block reads the block's entry and
       // decides alike, before the first barrier, whether the block plans it --
       // no helper waits for a chain that never starts
-      if (w.cand_floor >= 0) {
+      if (w.cand_floor() >= 0) {
         const int bi = static_cast<int>(blockIdx.x);
-        const int4 e = bi < w.n_list_head ? w.list_head[bi] : list[bi];
-        if (__builtin_amdgcn_readfirstlane(e.w) <= w.cand_floor) {
-          if (wave == 0) k2_skipped(w, __builtin_amdgcn_readfirstlane(e.x));
+        const int4 e = bi < w.n_list_head() ? wk.list_head[bi] : list[bi];
+        if (__builtin_amdgcn_readfirstlane(e.w) <= w.cand_floor()) {
+          if (wave == 0) k2_skipped(wk, __builtin_amdgcn_readfirstlane(e.x));
           return;
         }
       }
@@ -2804,10 +2909,10 @@ __global__ __launch_bounds__(256) void k2_node(DevWorkload w_arg, const int4* __
   const int li = __builtin_amdgcn_readfirstlane(nco + static_cast<int>((blockIdx.x - nco) * (blockDim.x >> 6)) + wave);
   if (li >= n_list) return;
   int4 xe = {-1, -1, -1, 0};
-  if (XT) xe = w.list_ext[li];  // issued with the entry: one round trip for both
+  if (XT) xe = wk.list_ext[li];  // issued with the entry: one round trip for both
   const K2Entry x = k2_entry<PROF>(w, list, li);
-  if (x.g <= w.cand_floor) {  // (a sequence round: judged before)
-    k2_skipped(w, x.ci);
+  if (x.g <= w.cand_floor()) {  // (a sequence round: judged before)
+    k2_skipped(wk, x.ci);
     return;
   }
   uint64_t* F = k2_lds + static_cast<size_t>(wave) * region;

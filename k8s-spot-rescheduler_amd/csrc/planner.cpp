@@ -680,12 +680,20 @@ sr_status fill_dev_workload(sr_ctx* ctx, Slot& sl) {
   d.pod_patch = p.n_pod_patch ? static_cast<const uint64_t*>(at(o.pod_patch)) : nullptr;
   d.n_pod_patch = p.n_pod_patch;
   d.k0_skip = p.skip ? 1 : 0;
+  // the changed nodes of a K0-less run, one table entry per lane of a K2 wave (DevWorkload::dirty_tab); they
+  // are the nodes of node_patch, in its order
   d.n_dirty = p.n_dirty;
   for (int32_t i = 0; i < p.n_dirty; ++i) {
-    d.dirty_node[i] = p.dirty_node[i];
-    for (int dm = 0; dm < 3; ++dm) d.dirty_free[i][dm] = p.dirty_free[i][dm];
+    for (int dm = 0; dm < 3; ++dm) d.dirty_tab[16 * dm + i] = p.dirty_free[i][dm];
+    const uint64_t* rec = tl.node_patch.data() + static_cast<size_t>(i) * sr::kNodePatchWords;
+    if (p.n_node_patch != p.n_dirty || rec[0] != static_cast<uint64_t>(p.dirty_node[i])) {
+      ctx->err = "K0-less run: the node patches are not the changed nodes";
+      return SR_ERR_STATE;
+    }
+    d.dirty_tab[48 + i] = static_cast<int64_t>(static_cast<uint64_t>(static_cast<uint32_t>(p.dirty_node[i])) |
+                                                 static_cast<uint64_t>(static_cast<uint32_t>(rec[5])) << 32);
   }
-  static_assert(sizeof(d.dirty_node) / sizeof(d.dirty_node[0]) == sr::kSkipDirty, "kSkipDirty nodes in the kernel arguments");
+  static_assert(sr::kSkipDirty == 16 && sizeof(d.dirty_tab) == 64 * 8, "kSkipDirty nodes x 4 entries in the kernel arguments");
   d.first_fallback_local = w.first_fallback;
   static_assert(sr::kPodPatchU64 == sr::kPodPatchWords && sr::kNodePatchU64 == sr::kNodePatchWords &&
                     sr::kTPad == sr::kTSpare,

@@ -14,7 +14,7 @@
 namespace sr {
 
 constexpr size_t kDirtyMax = 64;       // changed nodes tracked since the last K0 run (more: the list is dropped)
-constexpr size_t kSkipDirty = 16;      // ... a K0-less run carries (DevWorkload::dirty_node)
+constexpr size_t kSkipDirty = 16;      // ... a K0-less run carries (DevWorkload::dirty_tab)
 constexpr size_t kPatchNodes = 16;     // ... sent as node patches instead of the whole node section
 constexpr size_t kAtomsLogMax = 256;   // atom rows logged since the version both copies may lag to
 constexpr size_t kK0ColsMax = 32;      // word columns / T rows of an incremental K0 (more: every row)

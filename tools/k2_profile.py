@@ -21,7 +21,10 @@ cycles, and the high halves carry the split of the two sections that wait for
 table rows: [8] >> 32 the prologue's cycles from a batch's first load to its
 last one's return, [11] >> 32 the same for the far resolutions' chunk rounds
 (the rest of the section consumes the rows), [10] >> 32 the pods pending over
-all resolutions (16 bits) and the resolutions (16 bits above).
+all resolutions (16 bits) and the resolutions (16 bits above), [9] >> 32 the
+cycles from the pod records' arrival to the issue of the first F-head load
+(0: the wave loads none), [13] >> 32 the cycles from the entry of k2_finish to
+the issue of the wave's last store.
 The last of the widest runs in the file is summarised (earlier ones are
 warmup; narrower ones are prefix batches of sr_plan_first)."""
 import sys
@@ -44,9 +47,11 @@ def main():
     last_run = max(range(len(runs)), key=lambda i: (len(runs[i]), i))
     r = runs[last_run].astype(np.int64)
     nod = r[:, 5] == 2
-    split = np.zeros((len(r), 4), np.int64)  # prologue loads, resolve loads, pending pods, resolutions
-    split[nod] = np.stack([r[nod, 8] >> 32, r[nod, 11] >> 32, (r[nod, 10] >> 32) & 0xffff, r[nod, 10] >> 48], axis=1)
-    for c in (8, 10, 11):
+    # prologue loads, resolve loads, pending pods, resolutions, records -> first F-head load, finish
+    split = np.zeros((len(r), 6), np.int64)
+    split[nod] = np.stack([r[nod, 8] >> 32, r[nod, 11] >> 32, (r[nod, 10] >> 32) & 0xffff, r[nod, 10] >> 48,
+                           r[nod, 9] >> 32, r[nod, 13] >> 32], axis=1)
+    for c in (8, 9, 10, 11, 13):
         r[nod, c] &= 0xffffffff
     full = r
     k0 = k0s[last_run].astype(np.int64)
@@ -98,6 +103,9 @@ def main():
         print("node order: entry->records cycles p50/p90/max %s; prologue (F heads) cycles p50/p90/max %s" % (
             " ".join("%.0f" % x for x in np.percentile(q[:, 14], [50, 90, 100])),
             " ".join("%.0f" % x for x in np.percentile(q[:, 8], [50, 90, 100]))))
+        print("node order: records->first F-head load cycles p50/p90/max %s; finish (entry->last store) cycles "
+              "p50/p90/max %s" % (" ".join("%.0f" % x for x in np.percentile(split[nodeo, 4], [50, 90, 100])),
+                                  " ".join("%.0f" % x for x in np.percentile(split[nodeo, 5], [50, 90, 100]))))
         sv = max(1, vis.sum())
         print("node order: cycles/visit min+window %.0f, placement %.0f, pointer moves %.0f"
               % (q[:, 9].sum() / sv, q[:, 10].sum() / sv, q[:, 11].sum() / sv))
@@ -150,11 +158,12 @@ def main():
         res = full[:, 12] & ((1 << 40) - 1)
 
         def srow(c):
-            print("  %5d %6.2f %6.2f | %6d | %6d = %6d + %6d | %6d = %6d + %6d | %3d pods in %d resolutions, %d chunk rounds"
-                  % (c, end[c], dur[c], full[c, 14], full[c, 8], split[c, 0], full[c, 8] - split[c, 0], res[c], split[c, 1],
-                     res[c] - split[c, 1], split[c, 2], split[c, 3], (full[c, 12] >> 40) & 0xffff))
-        scols = ("wave end_us dur_us | entry->records | prologue = loads returned + consumed | "
-                 "resolve = loads returned + consumed | pending pods")
+            print("  %5d %6.2f %6.2f | %6d %6d | %6d = %6d + %6d | %6d = %6d + %6d | %6d | %3d pods in %d resolutions, "
+                  "%d chunk rounds"
+                  % (c, end[c], dur[c], full[c, 14], split[c, 4], full[c, 8], split[c, 0], full[c, 8] - split[c, 0], res[c],
+                     split[c, 1], res[c] - split[c, 1], split[c, 5], split[c, 2], split[c, 3], (full[c, 12] >> 40) & 0xffff))
+        scols = ("wave end_us dur_us | entry->records records->first F-head load | prologue = loads returned + "
+                 "consumed | resolve = loads returned + consumed | finish | pending pods")
         print("first drainable candidate: %d" % first_ok)
         print("candidates 0..first_ok: " + scols)
         for c in range(0, first_ok + 1):
