@@ -77,7 +77,7 @@ __device__ __forceinline__ void explain_reduce(int (*s_part)[kXCols], uint32_t m
 
 // --- the shortfall kernels (k_shortfall, k_shortfall_plan) ---
 
-static_assert(kXWaves == 4, "shortfall_blocks (explain_dev.hpp) counts four row words a block");
+static_assert(kXWaves == 4, "shortfall_blocks (explain_args.hpp) counts four row words a block");
 
 // The mask bit of a dimension: SR_SHORT_CPU / MEMORY / EPHEMERAL follow WHY_CPU.., SR_SHORT_PODS is WHY_PODS.
 __device__ __forceinline__ uint32_t short_bit(int d) { return d < 3 ? 1u << (WHY_CPU + d) : 1u << WHY_PODS; }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "explain_dev.hpp"
+#include "explain_stage.hpp"
 #include "host.hpp"
 #include "kernels.hpp"
 #include "residency.hpp"
@@ -202,12 +203,7 @@ struct sr_ctx {
   // the residency model, so a plan before and after an explain call encodes and uploads exactly the same
   sr::EncoderCache x_enc;
   sr::Workload x_wl;
-  sr::ExplainPrograms x_prog;
-  std::vector<sr::ExplainPod> x_pods;
-  std::vector<sr::PlanCtxEntry> x_centries;  // sr_explain_plan: the context lists, their offsets and the nodes'
-                                             //   pod slack as the kernel reads them
-  std::vector<int32_t> x_coff, x_slack;
-  std::vector<int64_t> x_left;  // sr_shortfall_*: the nodes' pod slack in 64 bits
+  sr::ExplainStage x_stage;  // what the call uploads, where each part of its two buffers lies (explain_stage.hpp)
   DevBuf x_in, x_out;
   HostBuf hx_in, hx_out;
 };
@@ -1845,14 +1841,6 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
 // kernels, read the nodes' pod slack in 64 bits (node_left, in the place of
 // node_slack) and leave per-block partials that k_shortfall_close closes on
 // the same stream; `out` gets what it gets without `sh`.
-static void shortfall_none(sr_shortfall_out* sh, size_t o, size_t ns) {  // a fallback pod, or one not asked
-  sh->near[o] = -1;
-  std::fill_n(sh->only_nodes + o * SR_SHORT_COUNT, SR_SHORT_COUNT, 0);
-  std::fill_n(sh->only_min + o * SR_SHORT_COUNT, SR_SHORT_COUNT, int64_t(0));
-  std::fill_n(sh->only_at + o * SR_SHORT_COUNT, SR_SHORT_COUNT, -1);
-  if (sh->node_short) std::fill_n(sh->node_short + o * ns * SR_SHORT_COUNT, ns * SR_SHORT_COUNT, int64_t(0));
-}
-
 static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
                          sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr,
                          sr_shortfall_out* sh = nullptr) {
@@ -1869,167 +1857,34 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
     ctx->err = err;
     return st;
   }
-  const int32_t n_spot = w.n_spot, na = static_cast<int32_t>(w.pod_src.size());
-  const size_t ns = static_cast<size_t>(n_spot);
-  for (int32_t i = 0; i < n; ++i) {  // a fallback pod: nothing evaluated
-    const bool fb = w.status_host[i] == SR_CAND_FALLBACK;
-    const size_t o = static_cast<size_t>(slot ? slot[i] : i);
-    out->feasible[o] = out->first[o] = -1;
-    std::fill_n(out->counts + o * SR_WHY_COUNT, SR_WHY_COUNT, 0);
-    if (out->node_mask) std::fill_n(out->node_mask + o * ns, ns, uint16_t(0));
-    if (out->fallback) out->fallback[o] = fb ? 1 : 0;
-    if (sh) shortfall_none(sh, o, ns);
-  }
-  if (na == 0) return SR_OK;
-  if (!sr::build_explain(w, &ctx->x_prog) || w.pod_cls.size() != static_cast<size_t>(na) || w.n_pad != w.Wp * 64 ||
-      ctx->x_enc.node_free.size() < 3 * static_cast<size_t>(w.n_pad)) {
-    ctx->err = "explain: the encoder left no reasons";
-    return SR_ERR_STATE;
-  }
-  sr::explain_pods(w, &ctx->x_pods);
-  for (const sr::ExplainPod& p : ctx->x_pods)
-    if (p.cls < 0 || p.cls >= w.n_classes) {
-      ctx->err = "explain: pod class out of range";
-      return SR_ERR_STATE;
-    }
-  for (int32_t op : ctx->x_prog.ops)  // what the kernel indexes with
-    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > sr::X_ALL) {
-      ctx->err = "explain: malformed program";
-      return SR_ERR_STATE;
-    }
-  // input: atoms | node_free | xoff | xops | pods [| context entries | context offsets | node slack] (8-byte
-  // aligned parts)
-  auto up8 = [](size_t b) { return (b + 7) & ~size_t(7); };
-  const size_t b_atoms = w.atoms.size() * sizeof(uint64_t), b_free = 3 * static_cast<size_t>(w.n_pad) * sizeof(int64_t);
-  const size_t b_off = up8(ctx->x_prog.off.size() * sizeof(int32_t)), b_ops = up8(ctx->x_prog.ops.size() * sizeof(int32_t));
-  const size_t b_pods = static_cast<size_t>(na) * sizeof(sr::ExplainPod);
-  const size_t o_free = b_atoms, o_off = o_free + b_free, o_ops = o_off + b_off, o_pods = o_ops + b_ops;
-  size_t b_ctx = 0, b_coff = 0, b_slack = 0;
-  if (pq) {  // the lists in active-pod order
-    ctx->x_coff.assign(1, 0);
-    ctx->x_centries.clear();
-    for (int32_t q = 0; q < na; ++q) {
-      const int32_t i = w.pod_src[q] - w.pod_base;
-      const auto e0 = pq->entries.begin();
-      ctx->x_centries.insert(ctx->x_centries.end(), e0 + pq->off[i], e0 + pq->off[i + 1]);
-      ctx->x_coff.push_back(static_cast<int32_t>(ctx->x_centries.size()));
-    }
-    for (const sr::PlanCtxEntry& e : ctx->x_centries)  // what the kernel indexes with
-      if (e.node < 0 || e.node >= n_spot) {
-        ctx->err = "explain: context node out of range";
-        return SR_ERR_STATE;
-      }
-    if (!sh) sr::node_slack(snap, w.n_pad, &ctx->x_slack);
-    b_ctx = ctx->x_centries.size() * sizeof(sr::PlanCtxEntry);
-    b_coff = up8(ctx->x_coff.size() * sizeof(int32_t));
-    if (!sh) b_slack = up8(ctx->x_slack.size() * sizeof(int32_t));
-  }
-  if (sh) {
-    sr::node_left(snap, w.n_pad, &ctx->x_left);
-    b_slack = ctx->x_left.size() * sizeof(int64_t);
-  }
-  const size_t o_ctx = o_pods + b_pods, o_coff = o_ctx + b_ctx, o_slack = o_coff + b_coff;
-  const size_t in_bytes = o_slack + b_slack;
-  const size_t b_sums = static_cast<size_t>(na) * sr::kExplainSums * sizeof(int32_t);
-  // output: sums [| shortfall sums | only_min | only_at | node_short] | masks [| the blocks' partials, which stay
-  // on the device]
-  const int32_t blocks = sr::shortfall_blocks(w.Wp);
-  const size_t b_ssums = sh ? static_cast<size_t>(na) * sr::kShortSums * sizeof(int32_t) : 0;
-  const size_t b_omin = sh ? static_cast<size_t>(na) * SR_SHORT_COUNT * sizeof(int64_t) : 0;
-  const size_t b_oat = sh ? static_cast<size_t>(na) * SR_SHORT_COUNT * sizeof(int32_t) : 0;
-  const size_t b_nshort = sh && sh->node_short ? static_cast<size_t>(na) * ns * SR_SHORT_COUNT * sizeof(int64_t) : 0;
-  const size_t o_ssums = b_sums, o_omin = o_ssums + b_ssums, o_oat = o_omin + b_omin, o_nshort = o_oat + b_oat;
-  const size_t o_masks = o_nshort + b_nshort;
-  const size_t out_bytes = o_masks + (out->node_mask ? static_cast<size_t>(na) * ns * sizeof(uint16_t) : 0);
-  const size_t o_pmin = up8(out_bytes);
-  const size_t b_pmin = sh ? static_cast<size_t>(na) * blocks * SR_SHORT_COUNT * sizeof(uint64_t) : 0;
-  const size_t o_pat = o_pmin + b_pmin, dev_out_bytes = sh ? o_pat + b_pmin / 2 : out_bytes;
+  for (int32_t i = 0; i < n; ++i)  // a fallback pod: nothing evaluated
+    sr::clear_slot(out, sh, static_cast<size_t>(slot ? slot[i] : i), static_cast<size_t>(w.n_spot),
+                   w.status_host[i] == SR_CAND_FALLBACK ? 1 : 0);
+  if (w.pod_src.empty()) return SR_OK;
+  sr::ExplainStage& x = ctx->x_stage;
+  st = x.plan(w, ctx->x_enc.node_free, snap, pq, sh != nullptr, out->node_mask != nullptr, sh && sh->node_short,
+              &ctx->err);
+  if (st != SR_OK) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
-  HIP_TRY(ctx, host_reserve(ctx->hx_in, in_bytes));
-  HIP_TRY(ctx, host_reserve(ctx->hx_out, out_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_in, in_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_out, dev_out_bytes));
-  char* h = static_cast<char*>(ctx->hx_in.p);
-  std::memcpy(h, w.atoms.data(), b_atoms);
-  std::memcpy(h + o_free, ctx->x_enc.node_free.data(), b_free);
-  std::memcpy(h + o_off, ctx->x_prog.off.data(), ctx->x_prog.off.size() * sizeof(int32_t));
-  std::memcpy(h + o_ops, ctx->x_prog.ops.data(), ctx->x_prog.ops.size() * sizeof(int32_t));
-  std::memcpy(h + o_pods, ctx->x_pods.data(), b_pods);
-  if (pq) {
-    if (b_ctx) std::memcpy(h + o_ctx, ctx->x_centries.data(), b_ctx);
-    std::memcpy(h + o_coff, ctx->x_coff.data(), ctx->x_coff.size() * sizeof(int32_t));
-    if (!sh) std::memcpy(h + o_slack, ctx->x_slack.data(), ctx->x_slack.size() * sizeof(int32_t));
-  }
-  if (sh) std::memcpy(h + o_slack, ctx->x_left.data(), b_slack);
-  char* d = static_cast<char*>(ctx->x_in.p);
-  HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, b_sums + b_ssums, ctx->stream));
-  sr::ExplainArgs a{};
-  a.n_spot = n_spot;
-  a.n_pad = w.n_pad;
-  a.Wp = w.Wp;
-  a.n_pods = na;
-  a.atoms = reinterpret_cast<const uint64_t*>(d);
-  a.node_free = reinterpret_cast<const int64_t*>(d + o_free);
-  a.xoff = reinterpret_cast<const int32_t*>(d + o_off);
-  a.xops = reinterpret_cast<const int32_t*>(d + o_ops);
-  a.pods = reinterpret_cast<const sr::ExplainPod*>(d + o_pods);
-  a.sums = static_cast<int32_t*>(ctx->x_out.p);
-  char* dout = static_cast<char*>(ctx->x_out.p);
-  a.node_mask = out->node_mask ? reinterpret_cast<uint16_t*>(dout + o_masks) : nullptr;
-  sr::ShortfallArgs sa{};
-  if (sh) {
-    sa.node_left = reinterpret_cast<const int64_t*>(d + o_slack);
-    sa.sums = reinterpret_cast<int32_t*>(dout + o_ssums);
-    sa.part_min = reinterpret_cast<uint64_t*>(dout + o_pmin);
-    sa.part_at = reinterpret_cast<int32_t*>(dout + o_pat);
-    sa.blocks = blocks;
-    sa.only_min = reinterpret_cast<int64_t*>(dout + o_omin);
-    sa.only_at = reinterpret_cast<int32_t*>(dout + o_oat);
-    sa.node_short = sh->node_short ? reinterpret_cast<int64_t*>(dout + o_nshort) : nullptr;
-  }
-  if (pq) {
-    sr::ExplainPlanArgs pa{};
-    pa.x = a;
-    pa.ctx = reinterpret_cast<const sr::PlanCtxEntry*>(d + o_ctx);
-    pa.ctx_off = reinterpret_cast<const int32_t*>(d + o_coff);
-    pa.node_slack = sh ? nullptr : reinterpret_cast<const int32_t*>(d + o_slack);
-    if (sh) HIP_TRY(ctx, sr::launch_shortfall_plan(pa, sa, ctx->stream));
-    else HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
-  } else if (sh) {
-    HIP_TRY(ctx, sr::launch_shortfall(a, sa, ctx->stream));
-  } else {
-    HIP_TRY(ctx, sr::launch_explain(a, ctx->stream));
-  }
-  if (sh) HIP_TRY(ctx, sr::launch_shortfall_close(na, sa, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
+  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().dev_out_bytes));
+  x.pack(static_cast<char*>(ctx->hx_in.p));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
+  sr::ExplainPlanArgs pa;
+  sr::ShortfallArgs sa;
+  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), &pa, &sa);
+  if (pq && sh) HIP_TRY(ctx, sr::launch_shortfall_plan(pa, sa, ctx->stream));
+  else if (pq) HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
+  else if (sh) HIP_TRY(ctx, sr::launch_shortfall(pa.x, sa, ctx->stream));
+  else HIP_TRY(ctx, sr::launch_explain(pa.x, ctx->stream));
+  if (sh) HIP_TRY(ctx, sr::launch_shortfall_close(x.n_pods(), sa, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t* sums = static_cast<const int32_t*>(ctx->hx_out.p);
-  const char* hout = static_cast<const char*>(ctx->hx_out.p);
-  const uint16_t* masks = reinterpret_cast<const uint16_t*>(hout + o_masks);
-  const int32_t* ssums = reinterpret_cast<const int32_t*>(hout + o_ssums);
-  const int64_t* omin = reinterpret_cast<const int64_t*>(hout + o_omin);
-  const int32_t* oat = reinterpret_cast<const int32_t*>(hout + o_oat);
-  const int64_t* nshort = reinterpret_cast<const int64_t*>(hout + o_nshort);
-  for (int32_t q = 0; q < na; ++q) {
-    const int32_t src = w.pod_src[q] - w.pod_base;
-    const size_t i = static_cast<size_t>(slot ? slot[src] : src);
-    const int32_t* s = sums + static_cast<size_t>(q) * sr::kExplainSums;
-    std::copy_n(s, SR_WHY_COUNT, out->counts + i * SR_WHY_COUNT);
-    out->feasible[i] = s[sr::kExplainFeasible];
-    out->first[i] = s[sr::kExplainFirst] > 0 ? w.n_pad - s[sr::kExplainFirst] : -1;
-    if (out->node_mask) std::copy_n(masks + q * ns, ns, out->node_mask + i * ns);
-    if (sh) {
-      sh->near[i] = ssums[static_cast<size_t>(q) * sr::kShortSums];
-      std::copy_n(ssums + static_cast<size_t>(q) * sr::kShortSums + 1, SR_SHORT_COUNT, sh->only_nodes + i * SR_SHORT_COUNT);
-      std::copy_n(omin + static_cast<size_t>(q) * SR_SHORT_COUNT, SR_SHORT_COUNT, sh->only_min + i * SR_SHORT_COUNT);
-      std::copy_n(oat + static_cast<size_t>(q) * SR_SHORT_COUNT, SR_SHORT_COUNT, sh->only_at + i * SR_SHORT_COUNT);
-      if (sh->node_short)
-        std::copy_n(nshort + static_cast<size_t>(q) * ns * SR_SHORT_COUNT, ns * SR_SHORT_COUNT,
-                    sh->node_short + i * ns * SR_SHORT_COUNT);
-    }
-  }
+  x.unpack(static_cast<const char*>(ctx->hx_out.p), slot, out, sh);
   return SR_OK;
 }
 
@@ -2094,14 +1949,8 @@ static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* 
   sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
   if (st != SR_OK) return st;
   const size_t ns = snap->nodes.size();
-  for (int32_t c = 0; c < nc; ++c) {  // not asked: as a fallback pod, but fallback = 0
-    if (pq.how[c] != SR_EXPLAIN_NONE) continue;
-    out->feasible[c] = out->first[c] = -1;
-    std::fill_n(out->counts + static_cast<size_t>(c) * SR_WHY_COUNT, SR_WHY_COUNT, 0);
-    if (out->node_mask) std::fill_n(out->node_mask + c * ns, ns, uint16_t(0));
-    if (out->fallback) out->fallback[c] = 0;
-    if (sh) shortfall_none(sh, static_cast<size_t>(c), ns);
-  }
+  for (int32_t c = 0; c < nc; ++c)  // not asked: as a fallback pod, but fallback = 0
+    if (pq.how[c] == SR_EXPLAIN_NONE) sr::clear_slot(out, sh, static_cast<size_t>(c), ns, 0);
   const int32_t nb = static_cast<int32_t>(pq.batched.size());
   st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data(), sh);
   if (st != SR_OK) return st;

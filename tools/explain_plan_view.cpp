@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../k8s-spot-rescheduler_amd/csrc/explain_plan.hpp"
+#include "../k8s-spot-rescheduler_amd/csrc/explain_stage.hpp"
 #include "../k8s-spot-rescheduler_amd/csrc/host.hpp"
 
 extern "C" {
@@ -86,10 +86,12 @@ sr_status sr_explain_plan_view(const sr_cluster* cluster, const sr_snapshot* sna
   std::vector<sr::ExplainPod> xp;
   if (!sr::build_explain(w, &x) || w.pod_cls.size() != static_cast<size_t>(na)) return SR_ERR_STATE;
   sr::explain_pods(w, &xp);
+  std::vector<sr::PlanCtxEntry> entries;  // the lists in active-pod order
+  std::vector<int32_t> eoff;
+  sr::active_lists(w, pq, &entries, &eoff);
   for (int32_t q = 0; q < na; ++q) {
-    const int32_t i = w.pod_src[q] - w.pod_base;
-    const sr::PlanCtxEntry *lo = pq.entries.data() + pq.off[i], *hi = pq.entries.data() + pq.off[i + 1];
-    uint16_t* row = node_mask + static_cast<size_t>(pq.batched[i]) * ns;
+    const sr::PlanCtxEntry *lo = entries.data() + eoff[q], *hi = entries.data() + eoff[q + 1];
+    uint16_t* row = node_mask + static_cast<size_t>(pq.batched[w.pod_src[q] - w.pod_base]) * ns;
     for (int32_t node = 0; node < static_cast<int32_t>(ns); ++node)
       row[node] = static_cast<uint16_t>(sr::explain_node_ctx(x, xp[q], w.atoms.data(), w.Wp, cache.node_free.data(),
                                                              w.n_pad, node, slack[node], sr::find_ctx(lo, hi, node)));
@@ -101,12 +103,12 @@ sr_status sr_explain_plan_view(const sr_cluster* cluster, const sr_snapshot* sna
 
 namespace {
 
-// `pods` as candidates of their own against `snap`, tags on; query i (into pods) with the context list
-// [off[i], off[i + 1]) of `entries` (off == nullptr: no contexts): every node's mask by explain_node_ctx and its
-// shortfalls by shortfall_node, into row slot[i] (nullptr: i) of node_mask / node_short; status[i] the encode's.
+// `pods` as candidates of their own against `snap`, tags on; query i (into pods) with context list i of `pq`
+// (nullptr: no contexts): every node's mask by explain_node_ctx and its shortfalls by shortfall_node, into row
+// slot[i] (nullptr: i) of node_mask / node_short; status[i] the encode's.
 sr_status shortfall_rows(const sr_cluster* cluster, const sr_snapshot* snap, const int32_t* pods, int32_t n,
-                         const int32_t* off, const sr::PlanCtxEntry* entries, const int32_t* slot, uint16_t* node_mask,
-                         int64_t* node_short, std::vector<int32_t>* status) {
+                         const sr::PlanQueries* pq, const int32_t* slot, uint16_t* node_mask, int64_t* node_short,
+                         std::vector<int32_t>* status) {
   status->assign(static_cast<size_t>(n), SR_CAND_OK);
   if (n == 0) return SR_OK;
   const size_t ns = snap->nodes.size();
@@ -130,12 +132,15 @@ sr_status shortfall_rows(const sr_cluster* cluster, const sr_snapshot* snap, con
   std::vector<int64_t> left;
   sr::node_slack(snap, std::max(w.n_pad, static_cast<int32_t>(ns)), &slack);
   sr::node_left(snap, std::max(w.n_pad, static_cast<int32_t>(ns)), &left);
+  std::vector<sr::PlanCtxEntry> entries;  // the lists in active-pod order
+  std::vector<int32_t> eoff;
+  if (pq) sr::active_lists(w, *pq, &entries, &eoff);
   for (int32_t q = 0; q < na; ++q) {
     const int32_t i = w.pod_src[q] - w.pod_base;
-    const sr::PlanCtxEntry *lo = off ? entries + off[i] : nullptr, *hi = off ? entries + off[i + 1] : nullptr;
     const size_t row = static_cast<size_t>(slot ? slot[i] : i) * ns;
     for (int32_t node = 0; node < static_cast<int32_t>(ns); ++node) {
-      const sr::PlanCtxEntry* e = off ? sr::find_ctx(lo, hi, node) : nullptr;
+      const sr::PlanCtxEntry* e =
+          pq ? sr::find_ctx(entries.data() + eoff[q], entries.data() + eoff[q + 1], node) : nullptr;
       const uint32_t m = sr::explain_node_ctx(x, xp[q], w.atoms.data(), w.Wp, cache.node_free.data(), w.n_pad, node,
                                               slack[node], e);
       node_mask[row + node] = static_cast<uint16_t>(m);
@@ -160,7 +165,7 @@ sr_status sr_shortfall_pods_view(const sr_cluster* cluster, const sr_snapshot* s
   std::fill_n(node_mask, static_cast<size_t>(n) * ns, uint16_t(0));
   std::fill_n(node_short, static_cast<size_t>(n) * ns * SR_SHORT_COUNT, int64_t(0));
   std::vector<int32_t> status;
-  const sr_status st = shortfall_rows(cluster, snap, pods, n, nullptr, nullptr, nullptr, node_mask, node_short, &status);
+  const sr_status st = shortfall_rows(cluster, snap, pods, n, nullptr, nullptr, node_mask, node_short, &status);
   if (st != SR_OK) return st;
   for (int32_t i = 0; i < n; ++i) fallback[i] = status[i] == SR_CAND_FALLBACK ? 1 : 0;
   return SR_OK;
@@ -183,8 +188,7 @@ sr_status sr_shortfall_plan_view(const sr_cluster* cluster, const sr_snapshot* s
   std::fill_n(node_short, static_cast<size_t>(nc) * ns * SR_SHORT_COUNT, int64_t(0));
   std::fill_n(fallback, nc, uint8_t(0));
   std::vector<int32_t> status;
-  st = shortfall_rows(cluster, snap, pq.pods.data(), nb, pq.off.data(), pq.entries.data(), pq.batched.data(), node_mask,
-                      node_short, &status);
+  st = shortfall_rows(cluster, snap, pq.pods.data(), nb, &pq, pq.batched.data(), node_mask, node_short, &status);
   if (st != SR_OK) return st;
   for (int32_t i = 0; i < nb; ++i) {
     if (status[i] != SR_CAND_FALLBACK) continue;
