@@ -25,6 +25,7 @@
 #include "host.hpp"
 #include "kernels.hpp"
 #include "residency.hpp"
+#include "result_words.hpp"
 #include "seq_pdb.hpp"
 
 #include <dlfcn.h>
@@ -101,7 +102,13 @@ struct sr_ctx {
   HostBuf h_result, h_status, h_node, h_bytes;
   HostBuf h_early;           // mapped: K2's per-candidate result words (single-rank runs)
   HostBuf h_comm;            // pinned: the reduced words of a caller-provided collective
-  bool in_flight = false;    // a run returned with K2 still planning candidates past the winner
+  // Device work of the last run may still be going (K2 planning the candidates past the winner, the ledger
+  // kernel, the cost copy); settle() waits for it before a buffer moves.  The one rule, for every way a run
+  // ends: set before the walk whenever device work of this run may outlive the call (also when the walk then
+  // fails); cleared if and only if a wait of this run synchronised the stream (ResultWait::synced), or
+  // copy_back did.  A run that ends with K3 leaves nothing behind once its words are there: K3 follows all
+  // of it in stream order and the words are its last stores.
+  bool in_flight = false;
   uint64_t* d_early = nullptr;  // device address of h_early
   uint64_t issued_checks = 0;  // checks of the prepared workload's plan (known after a full run)
   bool issued_known = false;
@@ -173,7 +180,8 @@ struct sr_ctx {
   // POSIX shared-memory segment holds, per rank and per tick parity, the
   // rank's published input words and the outcome words its K2 writes (mapped
   // into every rank's GPU); each rank's host walks them in global candidate
-  // order up to the first drainable one (no collective, no K3: DESIGN.md §7).
+  // order up to the first drainable one (no collective, no K3: result_words.hpp,
+  // DESIGN.md §7).
   struct Shm {
     uint64_t* host = nullptr;  // the segment (every rank's regions)
     uint64_t* dev = nullptr;   // its device address in this process
@@ -183,8 +191,6 @@ struct sr_ctx {
     uint64_t tick = 0;         // runs through the segment (identical on every rank)
     int32_t base = -1;         // the prepared call's first local candidate (cand_global[0] / nranks), -1: none
     std::string name;
-    std::vector<int32_t> act_of;  // scratch: active candidate of each input candidate
-    bool synced = false;       // the current run's walk waited for the stream (shm_wait): its K2 has finished
   } shm;
   sr_allreduce_min_fn host_fn = nullptr;  // sr_comm_init_host: the caller's allreduce(min)
   void* host_user = nullptr;
@@ -263,175 +269,42 @@ sr_status settle(sr_ctx* ctx) {
   return SR_OK;
 }
 
-bool has_comm(const sr_ctx* ctx) { return ctx->comm != nullptr || ctx->host_fn != nullptr || ctx->shm.host != nullptr; }
-
-// ---- the shared-memory transport (sr_comm_init_shm).  Per rank r and tick
-// parity p a region of kShmHdr + 2 * max_cand words, each word tag << 32 |
-// value (tag: the run's, identical on every rank):
-//   hdr[0] input candidates of the call   hdr[1] its first local index + 1 (0: none)
-//   hdr[2] first fallback (global) + 1    hdr[3] 1: the rank has finished this tick's walk
-//   hdr[4] smallest global index the rank has not planned after this call + 1 (0: none)
-//   in[i]  input candidate i: active candidate << 2 | 0, or 1 (no pods), 2 (fallback)
-//   st[ci] written by K2: active candidate ci is drainable (1) or not (0)
-constexpr size_t kShmHdr = 8;
-size_t shm_region_words(const sr_ctx* ctx) { return kShmHdr + 2 * static_cast<size_t>(ctx->shm.max_cand); }
-uint64_t* shm_region(sr_ctx* ctx, int32_t r, int p) {
-  return ctx->shm.host + (static_cast<size_t>(r) * 2 + static_cast<size_t>(p)) * shm_region_words(ctx);
-}
-// tags of the shared words: the high bit set, so they never equal a
-// single-rank run's (g_run_seq) in the context's private result words
-uint32_t shm_tag(const sr_ctx* ctx, uint64_t tick) {
-  return (ctx->shm.session + static_cast<uint32_t>(tick)) | 0x80000000u;
+// The stream fallback of a run's wait for its result words (sr::ResultWait): a failure is recorded as HIP_TRY
+// records it.
+bool sync_stream(void* user) {
+  sr_ctx* ctx = static_cast<sr_ctx*>(user);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) hip_fail(ctx, e, "hipStreamSynchronize(ctx->stream)");
+  return e == hipSuccess;
 }
 
-// Spins until ready().  A word of this rank's own K2 that has not arrived
-// after 100 ms is waited for on the stream (which surfaces a kernel fault);
-// another rank's after 60 s fails the run (that rank stopped planning).
-template <class F>
-sr_status shm_wait(sr_ctx* ctx, F ready, bool own, int32_t r) {
-  if (ready()) return SR_OK;
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  bool synced = false;
-  while (!ready()) {
-    if ((++spins & 1023) != 0) continue;
-    const auto dt = std::chrono::steady_clock::now() - t0;
-    if (own && !synced && dt > std::chrono::milliseconds(100)) {
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      synced = true;
-      ctx->shm.synced = true;
-      if (!ready()) {
-        ctx->err = "K2 outcome word not written by this run";
-        return SR_ERR_HIP;
-      }
-    } else if (!own && dt > std::chrono::seconds(60)) {
-      ctx->err = "rank " + std::to_string(r) + " published no outcome for this tick within 60 s";
+// How a wait or a walk over the result words ended, as the caller sees it.  missing: what to say of an own
+// word that was never written; silent_rank: ResultWait::silent_rank of a walk with peers.
+sr_status words_status(sr_ctx* ctx, sr::WordsStatus st, const char* missing, int32_t silent_rank = -1) {
+  switch (st) {
+    case sr::kWordsOk:
+      return SR_OK;
+    case sr::kWordsSyncFailed:  // (sync_stream said why)
+      return SR_ERR_HIP;
+    case sr::kWordsPeerSilent:
+      ctx->err = "rank " + std::to_string(silent_rank) + " published no outcome for this tick within 60 s";
       return SR_ERR_RCCL;
-    }
-  }
-  return SR_OK;
-}
-
-// Before K2: this rank's input words and header for the run's tick, into the
-// region of the tick's parity once every rank has finished walking the tick
-// that used it before; K2 then writes the outcome words there.
-sr_status shm_publish(sr_ctx* ctx, int* par) {
-  auto& S = ctx->shm;
-  sr::DevWorkload& d = ctx->dw;
-  const sr::Workload& w = ctx->cur->wl;
-  const uint64_t tick = ++S.tick;
-  const int p = static_cast<int>(tick & 1);
-  if (tick > 2) {
-    const uint64_t done = static_cast<uint64_t>(shm_tag(ctx, tick - 2)) << 32 | 1u;
-    for (int32_t r = 0; r < ctx->nranks; ++r) {
-      volatile uint64_t* hd = shm_region(ctx, r, p);
-      sr_status st = shm_wait(ctx, [&] { return hd[3] == done; }, false, r);
-      if (st != SR_OK) return st;
-    }
-  }
-  const uint32_t tag = shm_tag(ctx, tick);
-  ctx->seq = tag;
-  d.seq = tag;
-  const uint64_t T = static_cast<uint64_t>(tag) << 32;
-  volatile uint64_t* reg = shm_region(ctx, ctx->rank, p);
-  const int32_t n_in = w.n_input_cand;
-  S.act_of.assign(static_cast<size_t>(std::max(0, n_in)), -1);
-  for (int32_t ci = 0; ci < static_cast<int32_t>(w.cand_src.size()); ++ci) S.act_of[w.cand_src[ci]] = ci;
-  for (int32_t i = 0; i < n_in; ++i) {
-    const int32_t a = S.act_of[i];
-    reg[kShmHdr + i] = T | static_cast<uint32_t>(a >= 0 ? a << 2 : w.status_host[i] == SR_CAND_FALLBACK ? 2 : 1);
-  }
-  std::atomic_thread_fence(std::memory_order_release);
-  reg[0] = T | static_cast<uint32_t>(n_in);
-  reg[1] = T | static_cast<uint32_t>(n_in > 0 ? S.base + 1 : 0);
-  reg[2] = T | static_cast<uint32_t>(w.first_fallback + 1);
-  reg[4] = T | static_cast<uint32_t>(d.rank_next == ~0ull ? 0 : d.rank_next + 1);
-  d.res_stat = S.dev + (const_cast<uint64_t*>(reg) - S.host) + kShmHdr + S.max_cand;
-  d.res_map = ctx->d_early + d.n_cand;
-  *par = p;
-  return SR_OK;
-}
-
-// After K2: the walk in global candidate order over every rank's words (rank
-// g % N holds global index g): every index some rank planned in this call, in
-// ascending order, up to the first drainable one -- what allreduce(min) + K3
-// give; the result words are written as K3 would (`result`, tagged), the
-// owner's mapping from its K2 (rescheduler.go:280-286 stops at the first
-// drainable candidate, whichever rank planned it).
-sr_status shm_reduce(sr_ctx* ctx, int p) {
-  auto& S = ctx->shm;
-  const sr::Workload& w = ctx->cur->wl;
-  const uint32_t tag = ctx->dw.seq;
-  const int32_t N = ctx->nranks;
-  auto ready = [tag](volatile uint64_t* x) { return static_cast<uint32_t>(*x >> 32) == tag; };
-  std::vector<int64_t> n_r(static_cast<size_t>(N)), b_r(static_cast<size_t>(N));
-  int64_t ff = -1, nx = -1;
-  for (int32_t r = 0; r < N; ++r) {
-    volatile uint64_t* hd = shm_region(ctx, r, p);
-    for (int i : {0, 1, 2, 4}) {
-      sr_status st = shm_wait(ctx, [&] { return ready(hd + i); }, false, r);
-      if (st != SR_OK) return st;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    n_r[r] = static_cast<uint32_t>(hd[0]);
-    b_r[r] = static_cast<int64_t>(static_cast<uint32_t>(hd[1])) - 1;
-    const int64_t f = static_cast<int64_t>(static_cast<uint32_t>(hd[2])) - 1;
-    if (f >= 0) ff = ff < 0 ? f : std::min(ff, f);
-    const int64_t x = static_cast<int64_t>(static_cast<uint32_t>(hd[4])) - 1;
-    if (x >= 0) nx = nx < 0 ? x : std::min(nx, x);
-  }
-  int64_t first_ok = -1;
-  int32_t owner = -1, oci = -1;
-  // (the ranks' first local indices may differ: a merge of every rank's
-  // ascending indices, so an index no rank planned in this call is skipped)
-  std::vector<int64_t> at(static_cast<size_t>(N), 0);  // next input candidate of each rank
-  for (;;) {
-    int32_t r = -1;
-    int64_t g = INT64_MAX;
-    for (int32_t q = 0; q < N; ++q) {
-      if (at[q] >= n_r[q]) continue;
-      const int64_t gq = (b_r[q] + at[q]) * N + q;
-      if (gq < g) g = gq, r = q;
-    }
-    if (r < 0) break;  // every planned index walked
-    volatile uint64_t* reg = shm_region(ctx, r, p);
-    volatile uint64_t* in = reg + kShmHdr + at[r]++;
-    sr_status st = shm_wait(ctx, [&] { return ready(in); }, false, r);
-    if (st != SR_OK) return st;
-    const uint32_t v = static_cast<uint32_t>(*in);
-    if ((v & 3u) != 0) continue;  // no pods to move, or the reference path
-    const int32_t ci = static_cast<int32_t>(v >> 2);
-    volatile uint64_t* sw = reg + kShmHdr + S.max_cand + ci;
-    st = shm_wait(ctx, [&] { return ready(sw); }, r == ctx->rank, r);
-    if (st != SR_OK) return st;
-    if (static_cast<uint32_t>(*sw) & 1u) {
-      first_ok = g;
-      owner = r;
-      oci = ci;
+    case sr::kWordsNoCandidate:
+      ctx->err = "ledger result names no candidate of this round";
+      return SR_ERR_HIP;
+    case sr::kWordsNotWritten:
       break;
-    }
   }
-  shm_region(ctx, ctx->rank, p)[3] = static_cast<uint64_t>(tag) << 32 | 1u;  // this tick's words may be reused
-  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
-  const uint64_t T = static_cast<uint64_t>(tag) << 32;
-  int32_t np = 0;
-  if (owner == ctx->rank) {
-    const int32_t off = w.cand_off[oci];
-    np = w.cand_off[oci + 1] - off;
-    volatile uint64_t* map = static_cast<volatile uint64_t*>(ctx->h_early.p) + ctx->dw.n_cand + off;
-    for (int32_t q = 0; q < np; ++q) {
-      sr_status st = shm_wait(ctx, [&] { return ready(map + q); }, true, ctx->rank);
-      if (st != SR_OK) return st;
-      res[sr::kResultHeader + q] = T | static_cast<uint32_t>(map[q]);
-    }
-  }
-  res[0] = T | static_cast<uint32_t>(first_ok);
-  res[1] = T | (owner == ctx->rank ? 1u : 0u);
-  res[2] = T | static_cast<uint32_t>(np);
-  res[3] = T | static_cast<uint32_t>(ff);
-  res[4] = T | static_cast<uint32_t>(nx);
-  return SR_OK;
+  ctx->err = missing;
+  return SR_ERR_HIP;
 }
+
+sr::CandView cand_view(const sr::Workload& w) {
+  return sr::CandView{w.cand_src.data(), w.cand_off.data(), w.status_host.data(),
+                      static_cast<int32_t>(w.cand_global.size()), w.n_input_cand, w.max_cand_pods};
+}
+
+bool has_comm(const sr_ctx* ctx) { return ctx->comm != nullptr || ctx->host_fn != nullptr || ctx->shm.host != nullptr; }
 
 // allreduce(min) of n <= 8 uint64 words in device memory, stream-ordered:
 // RCCL in place, or the caller's collective on a pinned host copy.
@@ -804,57 +677,23 @@ sr_status flush_timing(sr_ctx* ctx) {
   return SR_OK;
 }
 
-// The end of a single-rank winner-only run: walk K2's per-candidate words in
-// candidate order up to the first drainable candidate, then read its mapping
-// (rescheduler.go:280-286 stops there too).  A run whose words have not all
-// arrived after 100 ms falls back to the stream, which also surfaces a kernel
-// fault as an error.
+// The end of a single-rank winner-only run (sr::walk_early): K2's words up to the first drainable candidate,
+// then its mapping.
 sr_status finish_early(sr_ctx* ctx, sr_plan_out* out) {
   const sr::Workload& w = ctx->cur->wl;
   const sr::DevWorkload& d = ctx->dw;
   if (ctx->timing_cur) ctx->t.n_runs += 1;
-  volatile uint64_t* stat = static_cast<volatile uint64_t*>(ctx->h_early.p);
-  volatile uint64_t* map = stat + d.n_cand;
-  const uint32_t tag = d.seq;
-  auto ready = [&](volatile uint64_t* p) { return static_cast<uint32_t>(*p >> 32) == tag; };
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  bool synced = false;
-  auto wait = [&](volatile uint64_t* p) -> sr_status {
-    while (!ready(p)) {
-      if (!synced && (++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        synced = true;
-      }
-      if (synced && !ready(p)) {
-        ctx->err = "K2 result word not written by this run";
-        return SR_ERR_HIP;
-      }
-    }
-    return SR_OK;
-  };
-  int32_t k = 0;
-  for (; k < d.n_cand; ++k) {
-    sr_status st = wait(stat + k);
-    if (st != SR_OK) return st;
-    if (static_cast<uint32_t>(stat[k]) == 1) break;
-  }
-  ctx->in_flight = !synced;
+  const volatile uint64_t* stat = static_cast<const volatile uint64_t*>(ctx->h_early.p);
+  ctx->in_flight = true;
+  sr::ResultWait wait(sync_stream, ctx);
+  const sr::Walk r = sr::walk_early(stat, stat + d.n_cand, cand_view(w), d.seq, wait);
+  if (wait.synced()) ctx->in_flight = false;
+  if (r.st != sr::kWordsOk) return words_status(ctx, r.st, "K2 result word not written by this run");
   out->first_fallback = w.first_fallback;
-  out->first_ok = k < d.n_cand ? w.cand_global[k] : -1;
+  out->first_ok = r.winner >= 0 ? w.cand_global[r.winner] : -1;
   out->winner = (out->first_ok >= 0 && (w.first_fallback < 0 || w.first_fallback > out->first_ok)) ? out->first_ok : -1;
-  out->winner_npods = 0;
-  if (k < d.n_cand) {
-    const int32_t o = w.cand_off[k], np = w.cand_off[k + 1] - o;
-    for (int32_t q = 0; q < np; ++q) {
-      sr_status st = wait(map + o + q);
-      if (st != SR_OK) return st;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    out->winner_npods = np;
-    if (out->winner_map)
-      for (int32_t q = 0; q < np; ++q) out->winner_map[q] = static_cast<int32_t>(static_cast<uint32_t>(map[o + q]));
-  }
+  out->winner_npods = r.np;
+  if (out->winner_map) sr::copy_values(r.map, r.np, out->winner_map);
   out->checks_dense = static_cast<uint64_t>(d.n_pods) * static_cast<uint64_t>(w.n_spot);
   out->fallback_pods = w.fallback_pods;
   out->checks = ctx->issued_known ? ctx->issued_checks : 0;
@@ -874,132 +713,30 @@ struct SeqWalk {
   int32_t stop = INT32_MAX;
 };
 
-// The first fallback candidate above the floor (INT32_MAX: none).
-int32_t first_fallback_above(const sr::Workload& w, int32_t floor) {
-  for (int32_t i = floor + 1; i < w.n_input_cand; ++i)
-    if (w.status_host[i] == SR_CAND_FALLBACK) return i;
-  return INT32_MAX;
-}
-
-// The end of a sequence round: as finish_early, but the walk over K2's
-// per-candidate words starts above the floor (the skipped candidates' waves
-// store no word and may be scheduled last: the work list is in cost order)
-// and takes the host-decided candidates in between (no pods: passed over; the
-// reference path: the walk stops there).
+// The end of a sequence round: K2's words above the floor (sr::walk_sequence), or under disruption budgets the
+// ledger step's (sr::walk_ledger: that step runs after the whole of K2, and K2 wrote no other candidate's
+// mapping to the host).  The ledger copy may still run when the words are there.
 sr_status finish_sequence(sr_ctx* ctx, SeqWalk* sq) {
   const sr::Workload& w = ctx->cur->wl;
   const sr::DevWorkload& d = ctx->dw;
   if (ctx->timing_cur) ctx->t.n_runs += 1;
-  volatile uint64_t* stat = static_cast<volatile uint64_t*>(ctx->h_early.p);
-  volatile uint64_t* map = stat + d.n_cand;
-  const uint32_t tag = d.seq;
-  auto ready = [&](volatile uint64_t* p) { return static_cast<uint32_t>(*p >> 32) == tag; };
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  bool synced = false;
-  auto wait = [&](volatile uint64_t* p) -> sr_status {
-    while (!ready(p)) {
-      if (!synced && (++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        synced = true;
-      }
-      if (synced && !ready(p)) {
-        ctx->err = "K2 result word not written by this run";
-        return SR_ERR_HIP;
-      }
-    }
-    return SR_OK;
-  };
-  ctx->in_flight = d.n_list > 0;  // (also when the walk fails)
-  sq->winner = sq->fallback = -1;
-  sq->end = w.n_input_cand - 1;
-  // the active candidates ascend in the caller's index (cand_src): k follows i
-  int32_t k = static_cast<int32_t>(std::upper_bound(w.cand_src.begin(), w.cand_src.end(), sq->floor) -
-                                   w.cand_src.begin());
-  for (int32_t i = sq->floor + 1; i < w.n_input_cand; ++i) {
-    if (k < d.n_cand && w.cand_src[k] == i) {
-      sr_status st = wait(stat + k);
-      if (st != SR_OK) return st;
-      if (static_cast<uint32_t>(stat[k]) == 1) {
-        sq->winner = sq->end = i;
-        break;
-      }
-      ++k;
-    } else if (w.status_host[i] == SR_CAND_FALLBACK) {
-      sq->fallback = i;
-      sq->end = i - 1;
-      break;
-    }
+  const volatile uint64_t* stat = static_cast<const volatile uint64_t*>(ctx->h_early.p);
+  const volatile uint64_t* res = static_cast<const volatile uint64_t*>(ctx->h_result.p);
+  ctx->in_flight = true;
+  sr::ResultWait wait(sync_stream, ctx);
+  const sr::Walk r = sq->pdb ? sr::walk_ledger(res, sr::kPdbHeader, cand_view(w), d.seq, sq->floor, sq->stop, wait)
+                             : sr::walk_sequence(stat, stat + d.n_cand, cand_view(w), d.seq, sq->floor, wait);
+  if (wait.synced()) ctx->in_flight = false;
+  sq->winner = r.winner;
+  sq->fallback = r.fallback;
+  sq->end = r.end;
+  if (r.st != sr::kWordsOk)
+    return words_status(ctx, r.st, sq->pdb ? "ledger result word not written by this round"
+                                           : "K2 result word not written by this run");
+  if (r.winner >= 0) {
+    sq->map.resize(static_cast<size_t>(r.np));
+    sr::copy_values(r.map, r.np, sq->map.data());
   }
-  if (sq->winner >= 0) {
-    const int32_t o = w.cand_off[k], np = w.cand_off[k + 1] - o;
-    for (int32_t q = 0; q < np; ++q) {
-      sr_status st = wait(map + o + q);
-      if (st != SR_OK) return st;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    sq->map.resize(static_cast<size_t>(np));
-    for (int32_t q = 0; q < np; ++q) sq->map[q] = static_cast<int32_t>(static_cast<uint32_t>(map[o + q]));
-  }
-  if (synced) ctx->in_flight = false;
-  return SR_OK;
-}
-
-// The end of a round under disruption budgets: the round's winner is the
-// ledger step's (seq_pdb.hip), not the first drainable candidate of K2's words
-// -- that one may be refused, and K2 wrote no other candidate's mapping to the
-// host.  The step runs after the whole of K2, so its words are waited for
-// instead of K2's.
-sr_status finish_sequence_pdb(sr_ctx* ctx, SeqWalk* sq) {
-  const sr::Workload& w = ctx->cur->wl;
-  const sr::DevWorkload& d = ctx->dw;
-  if (ctx->timing_cur) ctx->t.n_runs += 1;
-  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
-  const uint32_t tag = d.seq;
-  auto ready = [&](size_t i) { return static_cast<uint32_t>(res[i] >> 32) == tag; };
-  auto val = [&](size_t i) { return static_cast<int32_t>(static_cast<uint32_t>(res[i])); };
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  bool synced = false;
-  auto wait = [&](size_t i) -> sr_status {
-    while (!ready(i)) {
-      if (!synced && (++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        synced = true;
-      }
-      if (synced && !ready(i)) {
-        ctx->err = "ledger result word not written by this round";
-        return SR_ERR_HIP;
-      }
-    }
-    return SR_OK;
-  };
-  ctx->in_flight = true;  // the ledger copy may still run (also when the wait fails)
-  sq->winner = sq->fallback = -1;
-  sq->end = w.n_input_cand - 1;
-  for (size_t i = 0; i < static_cast<size_t>(sr::kPdbHeader); ++i) {
-    sr_status st = wait(i);
-    if (st != SR_OK) return st;
-  }
-  const int32_t win = val(0), np = val(1);
-  if (win >= 0) {
-    if (win <= sq->floor || win >= w.n_input_cand || np < 0 || np > w.max_cand_pods) {
-      ctx->err = "ledger result names no candidate of this round";
-      return SR_ERR_HIP;
-    }
-    for (int32_t q = 0; q < np; ++q) {
-      sr_status st = wait(static_cast<size_t>(sr::kPdbHeader + q));
-      if (st != SR_OK) return st;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    sq->map.resize(static_cast<size_t>(np));
-    for (int32_t q = 0; q < np; ++q) sq->map[q] = val(static_cast<size_t>(sr::kPdbHeader + q));
-    sq->winner = sq->end = win;
-  } else if (sq->stop != INT32_MAX) {
-    sq->fallback = sq->stop;
-    sq->end = sq->stop - 1;
-  }
-  if (synced) ctx->in_flight = false;
   return SR_OK;
 }
 
@@ -1111,7 +848,7 @@ sr_status queue_sequence(sr_ctx* ctx, const sr::Workload& w, const SeqWalk& sq) 
   r.in_off = static_cast<const int32_t*>(ctx->seq_off.p);
   r.n_cand = d.n_cand;
   r.floor = sq.floor;
-  r.fb_stop = first_fallback_above(w, sq.floor);
+  r.fb_stop = sr::first_fallback_above(cand_view(w), sq.floor);
   r.seq_status = static_cast<int32_t*>(ctx->seq_status.p);
   r.seq_node = static_cast<int32_t*>(ctx->seq_node.p);
   HIP_TRY(ctx, sr::launch_sequence(r, ctx->stream));
@@ -1183,49 +920,50 @@ sr_status copy_back(sr_ctx* ctx, bool full) {
   return SR_OK;
 }
 
-// Every result word carries this run's sequence number in its upper half (K3
-// stores them without ordering): poll the header, then the winner's mapping,
-// instead of waking up on stream completion.  A run that has not finished
-// after 100 ms falls back to the stream (which also surfaces a kernel fault as
-// an error).
+// A winner-only run that ends with K3: its header, then the winner's mapping, polled instead of waking up on
+// stream completion (sr::poll_header; a header still missing after the stream fallback is read_result's error).
 sr_status poll_result(sr_ctx* ctx) {
-  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
-  const uint32_t tag = static_cast<uint32_t>(ctx->dw.seq);
-  auto ready = [&](size_t i) { return static_cast<uint32_t>(res[i] >> 32) == tag; };
-  auto header_ready = [&] { return ready(0) && ready(1) && ready(2) && ready(3) && ready(4); };
-  auto map_ready = [&] {
-    if (!static_cast<uint32_t>(res[1])) return true;
-    const size_t np = static_cast<uint32_t>(res[2]);
-    for (size_t q = 0; q < np; ++q)
-      if (!ready(sr::kResultHeader + q)) return false;
-    return true;
-  };
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  while (!(header_ready() && map_ready())) {
-    if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) {
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  sr::ResultWait wait(sync_stream, ctx);
+  const sr::WordsStatus st = sr::poll_header(static_cast<const volatile uint64_t*>(ctx->h_result.p),
+                                             sr::kResultHeader, ctx->dw.seq, wait);
+  return words_status(ctx, st, "result header not written by this run");
+}
+
+// The shared-memory transport, before K2: this rank's input words and header for the run's tick (its tag is the
+// run's), once every rank has finished the tick that used the region before; K2 writes its outcome words there.
+sr_status shm_publish(sr_ctx* ctx, int* par) {
+  auto& S = ctx->shm;
+  sr::DevWorkload& d = ctx->dw;
+  const sr::Workload& w = ctx->cur->wl;
+  const sr::ShmSeg seg{S.host, S.max_cand, ctx->nranks, ctx->rank, S.session};
+  sr::ResultWait wait(sync_stream, ctx);  // (other ranks' words only)
+  const sr::ShmPublished pub = sr::shm_publish(seg, ++S.tick, cand_view(w), S.base, w.first_fallback, d.rank_next, wait);
+  SR_TRY(words_status(ctx, pub.st, "", wait.silent_rank()));
+  ctx->seq = d.seq = pub.tag;
+  d.res_stat = S.dev + (pub.stat - S.host);
+  d.res_map = ctx->d_early + d.n_cand;
+  *par = pub.p;
   return SR_OK;
 }
 
-// The shared-memory transport: every rank's outcome words in global order
-// (ms_collective: this host walk).  A winner-only walk returns at the winner:
-// this rank's K2 may still plan the candidates after it (res_map in h_early,
-// out_status, out_bytes, out_cycles), as after finish_early; the next prepare
-// settles before it moves a buffer.  Not after a wait that synchronised the
-// stream (copy_back: `waited`, or shm_wait).
+// ... after K2: every rank's outcome words in global order into the result words, as K3 would write them
+// (sr::shm_reduce; ms_collective: this host walk).  A winner-only walk returns at the winner: this rank's K2 may
+// still plan the candidates after it (res_map in h_early, out_status, out_bytes, out_cycles), as after
+// finish_early.  `waited`: copy_back has synchronised the stream.
 sr_status walk_shm(sr_ctx* ctx, int shm_par, bool waited) {
   const auto t0 = std::chrono::steady_clock::now();
-  ctx->shm.synced = false;
-  if (!waited) ctx->in_flight = true;  // (also when the walk fails: another rank's words missing)
-  SR_TRY(shm_reduce(ctx, shm_par));
-  if (!waited) ctx->in_flight = !ctx->shm.synced;
-  if (ctx->timing_cur & 4)
-    ctx->t.ms_collective += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const auto& S = ctx->shm;
+  const sr::ShmSeg seg{S.host, S.max_cand, ctx->nranks, ctx->rank, S.session};
+  if (!waited) ctx->in_flight = true;
+  sr::ResultWait wait(sync_stream, ctx);
+  const sr::WordsStatus st =
+      sr::shm_reduce(seg, shm_par, ctx->dw.seq, cand_view(ctx->cur->wl),
+                     static_cast<const volatile uint64_t*>(ctx->h_early.p) + ctx->dw.n_cand,
+                     static_cast<volatile uint64_t*>(ctx->h_result.p), sr::kResultHeader, wait);
+  if (wait.synced()) ctx->in_flight = false;
+  SR_TRY(words_status(ctx, st, "K2 outcome word not written by this run", wait.silent_rank()));
+  const auto t1 = std::chrono::steady_clock::now();
+  if (ctx->timing_cur & 4) ctx->t.ms_collective += std::chrono::duration<double, std::milli>(t1 - t0).count();
   return SR_OK;
 }
 
@@ -1235,21 +973,14 @@ sr_status read_result(sr_ctx* ctx, sr_plan_out* out, bool full) {
   const sr::Workload& w = ctx->cur->wl;
   const sr::DevWorkload& d = ctx->dw;
   const int32_t na = d.n_pods, ncand = d.n_cand;
-  volatile uint64_t* res = static_cast<volatile uint64_t*>(ctx->h_result.p);
-  auto val = [&](size_t i) { return static_cast<int32_t>(static_cast<uint32_t>(res[i])); };
-  const uint32_t tag = static_cast<uint32_t>(d.seq);
-  for (size_t i = 0; i < 5; ++i)
-    if (static_cast<uint32_t>(res[i] >> 32) != tag) {
-      ctx->err = "result header not written by this run";
-      return SR_ERR_HIP;
-    }
-  out->first_ok = val(0);
-  out->first_fallback = val(3);
-  ctx->last_rank_next = val(4);
-  out->winner = (val(0) >= 0 && (val(3) < 0 || val(3) > val(0))) ? val(0) : -1;
-  out->winner_npods = val(1) ? val(2) : 0;
-  if (out->winner_map && val(1))
-    for (int32_t q = 0; q < val(2); ++q) out->winner_map[q] = val(sr::kResultHeader + q);
+  const sr::Header h = sr::read_header(static_cast<const volatile uint64_t*>(ctx->h_result.p), sr::kResultHeader, d.seq);
+  SR_TRY(words_status(ctx, h.st, "result header not written by this run"));
+  out->first_ok = h.first_ok;
+  out->first_fallback = h.first_fallback;
+  ctx->last_rank_next = h.rank_next;
+  out->winner = (h.first_ok >= 0 && (h.first_fallback < 0 || h.first_fallback > h.first_ok)) ? h.first_ok : -1;
+  out->winner_npods = h.np;
+  if (out->winner_map) sr::copy_values(h.map, h.np, out->winner_map);
   out->checks_dense = static_cast<uint64_t>(na) * static_cast<uint64_t>(w.n_spot);
   out->fallback_pods = w.fallback_pods;
   if (full) {
@@ -1346,11 +1077,7 @@ sr_status run(sr_ctx* ctx, sr_plan_out* out, bool full, bool use_comm, SeqWalk* 
     sl.res.cost_queued(w);
   }
   if (sq) {  // a sequence round: the ledger after K2, then the walk
-    if (sq->pdb) {
-      SR_TRY(queue_sequence_pdb(ctx, *sq));
-      return finish_sequence_pdb(ctx, sq);
-    }
-    SR_TRY(queue_sequence(ctx, w, *sq));
+    SR_TRY(sq->pdb ? queue_sequence_pdb(ctx, *sq) : queue_sequence(ctx, w, *sq));
     return finish_sequence(ctx, sq);
   }
   if (early) return finish_early(ctx, out);
@@ -1693,7 +1420,7 @@ static sr_status plan_sequence(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster*
     } else {  // every candidate above the cursor is decided by the host
       sq.winner = sq.fallback = -1;
       sq.end = n - 1;
-      const int32_t fb = limited ? sq.stop : first_fallback_above(w, cursor);
+      const int32_t fb = limited ? sq.stop : sr::first_fallback_above(cand_view(w), cursor);
       if (fb != INT32_MAX) sq.fallback = fb, sq.end = fb - 1;
     }
     for (int32_t i = cursor + 1; i <= sq.end; ++i) {
@@ -2034,7 +1761,7 @@ sr_status sr_comm_init_shm(sr_ctx* ctx, const char* name, uint32_t session, int3
       max_cand > (1 << 28) || has_comm(ctx))
     return SR_ERR_INVALID_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return SR_ERR_HIP;
-  const size_t words = static_cast<size_t>(nranks) * 2 * (kShmHdr + 2 * static_cast<size_t>(max_cand));
+  const size_t words = static_cast<size_t>(nranks) * 2 * sr::shm_region_words(max_cand);
   const size_t bytes = (words * sizeof(uint64_t) + 4095) & ~size_t(4095);
   const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);
   if (fd < 0) {
