@@ -517,7 +517,8 @@ const char *sr_build_info(void);
  * sr_explain_candidate were added under ABI 11: two new functions, no struct
  * changed its layout; sr_explain_plan likewise: one more function;
  * sr_shortfall_pods and sr_shortfall_plan likewise: two functions and one new
- * output struct, sr_shortfall_out). */
+ * output struct, sr_shortfall_out; sr_node_view_pods and sr_node_view_plan
+ * likewise: two functions and one new output struct, sr_node_view_out). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -697,6 +698,55 @@ sr_status sr_shortfall_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const
                             const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
                             sr_explain_out *why /* optional */, sr_shortfall_out *out,
                             uint8_t *out_how /* optional [n_cand] */);
+
+/* "What does each spot node refuse": the masks and shortfalls of the two
+ * families above, reduced along the other axis -- per spot node over the
+ * queries -- on the device, so that no [n][n_spot] array is built anywhere
+ * (DESIGN.md 1.2, 4.1).
+ *   mask of a query on a node   exactly the mask sr_explain_pods (for
+ *       sr_node_view_pods) or sr_explain_plan (for sr_node_view_plan) gives:
+ *       for the latter each candidate's stop pod is judged in its own context;
+ *   shortfall   exactly sr_shortfall_*'s node_short value (pods saturate at
+ *       INT64_MAX); R as in the comment above;
+ *   slot   a query's asked index (_pods) or its candidate's local position
+ *       (_plan);
+ *   judged query   asked and inside the encoded predicate set.  Fallback pods
+ *       and candidates not asked (at_pod[c] < 0) are counted nowhere.
+ * For every spot node: admits counts the judged queries with mask 0 there,
+ * near those with m != 0 and (m & ~R) == 0, refuses[r] those whose mask holds
+ * bit r, sole[r] those whose mask is exactly bit r.  sole_min[d] / sole_at[d]
+ * is the lexicographic minimum of (shortfall, slot) over the queries whose
+ * mask on the node is exactly the bit of dimension d: the smallest such
+ * shortfall and the lowest slot attaining it, whatever order the device took
+ * the queries in; 0 / -1 when there is none.  With no judged query every count
+ * is 0, every sole_at -1 and *judged 0; n == 0 is SR_OK. */
+typedef struct {
+  int32_t *judged;     /* [1] queries evaluated: asked, inside the encoded predicate set */
+  int32_t *admits;     /* [n_spot] judged queries whose mask on the node is 0 */
+  int32_t *near;       /* [n_spot] ... for which the node is a near miss (m != 0, (m & ~R) == 0) */
+  int32_t *refuses;    /* [n_spot][SR_WHY_COUNT] ... whose mask on the node holds the bit */
+  int32_t *sole;       /* [n_spot][SR_WHY_COUNT] ... whose mask on the node is exactly that bit */
+  int64_t *sole_min;   /* [n_spot][SR_SHORT_COUNT] smallest shortfall among the queries whose mask on the node is
+                          exactly the bit of dimension d; 0 when none */
+  int32_t *sole_at;    /* [n_spot][SR_SHORT_COUNT] lowest query slot attaining it; -1 when none */
+  uint8_t *fallback;   /* optional [n] 1: outside the encoded set, counted nowhere */
+} sr_node_view_out;
+
+/* The pods judged against the snapshot as it is.  Arguments, errors and what
+ * is left untouched as for sr_explain_pods; every array of `out` but fallback
+ * is required (a NULL one is SR_ERR_INVALID_ARG). */
+sr_status sr_node_view_pods(sr_ctx *ctx, const sr_snapshot *snap, const sr_cluster *cluster, const int32_t *pods,
+                            int32_t n, sr_node_view_out *out);
+/* The stuck candidates of a tick, each stop pod in the context of its earlier
+ * pods; fallback is [n_cand].  Everything else (argument errors, SR_ERR_STATE
+ * on a forked snapshot, the two ways and out_how, the snapshot restored on
+ * every path, no collective, nothing of the planning side touched) as for
+ * sr_explain_plan.  The environment variable SR_NODE_VIEW_CHUNK (queries a
+ * block folds before it writes a partial, read per call) overrides the
+ * choice of both calls; results do not depend on it. */
+sr_status sr_node_view_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
+                            const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
+                            sr_node_view_out *out, uint8_t *out_how /* optional [n_cand] */);
 
 /* The planning segment as run() executes it (rescheduler.go:228-287): the
  * candidates in order until the first whose plan succeeds (drain + break,

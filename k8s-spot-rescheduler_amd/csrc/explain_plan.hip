@@ -39,25 +39,8 @@ __global__ __launch_bounds__(kXThreads) void k_explain_plan(ExplainPlanArgs pa) 
     bool pods_judged;
     mask = explain_walk(a, p.cls, word, lane, &pods_judged);
     // the context entries of this word: [first entry with node >= 64 word, first with node >= 64 (word + 1))
-    const int c0 = pa.ctx_off[q], c1 = pa.ctx_off[q + 1];
-    int touched = 0;  // earlier pods on the lane's node
-    int64_t acc[3] = {0, 0, 0};
-    if (c0 < c1) {
-      int lo = c0, hi = c1;
-      while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (pa.ctx[mid].node < word * 64) lo = mid + 1;
-        else hi = mid;
-      }
-      for (int i = lo; i < c1; ++i) {
-        const int en = pa.ctx[i].node;
-        if (en >= word * 64 + 64) break;
-        if (en == node) {
-          touched = pa.ctx[i].pods;
-          for (int d = 0; d < 3; ++d) acc[d] = pa.ctx[i].acc[d];
-        }
-      }
-    }
+    int64_t acc[3];
+    const int touched = explain_touched(pa, q, word, node, acc);  // earlier pods on the lane's node
     if (touched > 0 && pods_judged)
       mask = (mask & ~(1u << WHY_PODS)) | (pa.node_slack[node] - touched < 1 ? 1u << WHY_PODS : 0u);
     if (p.resources) {  // node < n_pad = 64 Wp: the pads hold INT64_MIN, are never touched and are cleared below
@@ -90,25 +73,8 @@ __global__ __launch_bounds__(kXThreads) void k_shortfall_plan(ExplainPlanArgs pa
     const ExplainPod p = a.pods[q];
     bool pods_judged;
     mask = explain_walk(a, p.cls, word, lane, &pods_judged);
-    const int c0 = pa.ctx_off[q], c1 = pa.ctx_off[q + 1];
-    int touched = 0;
-    int64_t acc[3] = {0, 0, 0};
-    if (c0 < c1) {
-      int lo = c0, hi = c1;
-      while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (pa.ctx[mid].node < word * 64) lo = mid + 1;
-        else hi = mid;
-      }
-      for (int i = lo; i < c1; ++i) {
-        const int en = pa.ctx[i].node;
-        if (en >= word * 64 + 64) break;
-        if (en == node) {
-          touched = pa.ctx[i].pods;
-          for (int d = 0; d < 3; ++d) acc[d] = pa.ctx[i].acc[d];
-        }
-      }
-    }
+    int64_t acc[3];
+    const int touched = explain_touched(pa, q, word, node, acc);
     if (valid) {
       const int64_t left = sa.node_left[node];
       if (touched > 0 && pods_judged)

@@ -67,7 +67,11 @@ const T* at_part(const char* base, const StagePart& p) {
 
 sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap,
                              const PlanQueries* pq, bool want_shortfall, bool node_mask, bool node_short,
-                             std::string* err) {
+                             std::string* err, const NodeViewAsk* view) {
+  if (view) {
+    want_shortfall = true;
+    node_mask = node_short = false;
+  }
   const size_t na = w.pod_src.size(), ns = static_cast<size_t>(w.n_spot), n_pad = static_cast<size_t>(w.n_pad);
   if (!build_explain(w, &prog_) || w.pod_cls.size() != na || w.n_pad != w.Wp * 64 || node_free.size() < 3 * n_pad) {
     *err = "explain: the encoder left no reasons";
@@ -101,6 +105,13 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
   shortfall_ = want_shortfall;
   want_mask_ = node_mask;
   want_short_ = want_shortfall && node_short;
+  view_ = view != nullptr;
+  chunks_ = NodeViewChunks{};
+  slots_.clear();
+  if (view_) {
+    chunks_ = node_view_chunks(w.Wp, n_pods_, view->per);
+    for (int32_t src : w.pod_src) slots_.push_back(view->slot ? view->slot[src - w.pod_base] : src - w.pod_base);
+  }
 
   at_ = StageLayout{};
   part_of(&at_.in[IN_ATOMS], &src_[IN_ATOMS], w.atoms.data(), w.atoms.size());
@@ -113,9 +124,14 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
   if (shortfall_) part_of(&at_.in[IN_SLACK], &src_[IN_SLACK], left_.data(), left_.size());
   else part_of(&at_.in[IN_SLACK], &src_[IN_SLACK], slack_.data(), lists_ ? slack_.size() : 0);
   at_.in_bytes = up8(place(at_.in, IN_PARTS));
+  if (view_) {  // behind the parts every call has: their layout is what it is without the switch
+    part_of(&at_.view_slot, nullptr, slots_.data(), slots_.size());
+    at_.view_slot.off = at_.in_bytes;
+    at_.in_bytes = up8(at_.view_slot.off + at_.view_slot.bytes);
+  }
 
-  const size_t sf = shortfall_ ? na : 0, dims = SR_SHORT_COUNT;
-  part_of<int32_t>(&at_.out[OUT_SUMS], nullptr, nullptr, na * kExplainSums);
+  const size_t sf = shortfall_ && !view_ ? na : 0, dims = SR_SHORT_COUNT;
+  part_of<int32_t>(&at_.out[OUT_SUMS], nullptr, nullptr, view_ ? 0 : na * kExplainSums);
   part_of<int32_t>(&at_.out[OUT_SSUMS], nullptr, nullptr, sf * kShortSums);
   part_of<int64_t>(&at_.out[OUT_OMIN], nullptr, nullptr, sf * dims);
   part_of<int32_t>(&at_.out[OUT_OAT], nullptr, nullptr, sf * dims);
@@ -127,12 +143,19 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
   at_.zero_bytes = at_.out[OUT_OMIN].off;
   at_.out_bytes = at_.out[OUT_MASKS].off + at_.out[OUT_MASKS].bytes;
   at_.dev_out_bytes = shortfall_ ? end : at_.out_bytes;
+  if (view_) {  // every per-query part is absent (end == 0): the partials are the buffer
+    part_of<uint64_t>(&at_.view_part, nullptr, nullptr,
+                      node_view_layout(n_pad, static_cast<size_t>(chunks_.chunks)).bytes / 8);
+    at_.view_part.off = up8(end);
+    at_.dev_out_bytes = at_.view_part.off + at_.view_part.bytes;
+  }
   return SR_OK;
 }
 
 void ExplainStage::pack(char* in) const {
   for (int i = 0; i < IN_PARTS; ++i)
     if (at_.in[i].bytes) std::memcpy(in + at_.in[i].off, src_[i], at_.in[i].bytes);
+  if (at_.view_slot.bytes) std::memcpy(in + at_.view_slot.off, slots_.data(), at_.view_slot.bytes);
 }
 
 void ExplainStage::args(const char* in, char* out, ExplainPlanArgs* pa, ShortfallArgs* sa) const {
@@ -165,6 +188,28 @@ void ExplainStage::args(const char* in, char* out, ExplainPlanArgs* pa, Shortfal
     sa->only_at = at_part<int32_t>(out, at_.out[OUT_OAT]);
     sa->node_short = want_short_ ? at_part<int64_t>(out, at_.out[OUT_NSHORT]) : nullptr;
   }
+}
+
+void ExplainStage::view_args(const char* in, char* out, char* totals, ExplainPlanArgs* pa, NodeViewArgs* na) const {
+  ShortfallArgs sa;
+  args(in, out, pa, &sa);
+  pa->x.sums = nullptr;  // (no per-query output is laid out)
+  *na = NodeViewArgs{};
+  na->node_left = at_part<int64_t>(in, at_.in[IN_SLACK]);
+  na->slot = at_part<int32_t>(in, at_.view_slot);
+  na->per = chunks_.per;
+  na->chunks = chunks_.chunks;
+  na->lists = lists_ ? 1 : 0;
+  na->tot_stride = node_view_stride(w_->n_spot);
+  const NodeViewLayout pl = node_view_layout(static_cast<size_t>(w_->n_pad), static_cast<size_t>(chunks_.chunks));
+  char* part = out + at_.view_part.off;
+  na->part_min = reinterpret_cast<uint64_t*>(part + pl.min);
+  na->part_cnt = reinterpret_cast<int32_t*>(part + pl.cnt);
+  na->part_at = reinterpret_cast<int32_t*>(part + pl.at);
+  const NodeViewLayout tl = node_view_layout(static_cast<size_t>(na->tot_stride), 1);
+  na->tot_min = reinterpret_cast<uint64_t*>(totals + tl.min);
+  na->tot_cnt = reinterpret_cast<int32_t*>(totals + tl.cnt);
+  na->tot_at = reinterpret_cast<int32_t*>(totals + tl.at);
 }
 
 void ExplainStage::unpack(const char* image, const int32_t* slot, sr_explain_out* out, sr_shortfall_out* sh) const {

@@ -43,6 +43,32 @@ __device__ __forceinline__ uint32_t explain_walk(const ExplainArgs& a, int cls, 
   return mask;
 }
 
+// The context entry of the lane's node in query q's list: the entries of the wave's own word lie contiguously,
+// the wave finds the first with a wave-uniform binary search and walks them with wave-uniform loads, and the
+// lane owning an entry's node keeps it.  Returns the earlier pods on the node (0: untouched, acc zeros).
+__device__ __forceinline__ int explain_touched(const ExplainPlanArgs& pa, int q, int word, int node, int64_t acc[3]) {
+  const int c0 = pa.ctx_off[q], c1 = pa.ctx_off[q + 1];
+  int touched = 0;
+  acc[0] = acc[1] = acc[2] = 0;
+  if (c0 < c1) {
+    int lo = c0, hi = c1;
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (pa.ctx[mid].node < word * 64) lo = mid + 1;
+      else hi = mid;
+    }
+    for (int i = lo; i < c1; ++i) {
+      const int en = pa.ctx[i].node;
+      if (en >= word * 64 + 64) break;
+      if (en == node) {
+        touched = pa.ctx[i].pods;
+        for (int d = 0; d < 3; ++d) acc[d] = pa.ctx[i].acc[d];
+      }
+    }
+  }
+  return touched;
+}
+
 constexpr int kXThreads = 256, kXWaves = kXThreads / 64;
 constexpr int kXCols = SR_WHY_COUNT + 2;  // per wave: a count per reason, feasible nodes, first feasible
 

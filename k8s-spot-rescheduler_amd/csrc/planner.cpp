@@ -212,6 +212,10 @@ struct sr_ctx {
   sr::ExplainStage x_stage;  // what the call uploads, where each part of its two buffers lies (explain_stage.hpp)
   DevBuf x_in, x_out;
   HostBuf hx_in, hx_out;
+  // sr_node_view_*: the call's per-node totals, which every pass of one call accumulates into (x_out may be
+  // allocated anew between the passes)
+  DevBuf x_view;
+  HostBuf hx_view;
 };
 
 namespace {
@@ -1163,7 +1167,7 @@ void sr_destroy(sr_ctx* ctx) {
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
                     &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off, &ctx->pdb_need, &ctx->pdb_remaining,
-                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out})
+                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out, &ctx->x_view})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1172,7 +1176,8 @@ void sr_destroy(sr_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->out_cycles.p) (void)hipFree(ctx->out_cycles.p);
   for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm,
-                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb, &ctx->hx_in, &ctx->hx_out})
+                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb, &ctx->hx_in, &ctx->hx_out,
+                     &ctx->hx_view})
     if (b->p) (void)hipHostFree(b->p);
   for (auto& sl : ctx->slots) {
     if (sl->arena.p) (void)hipFree(sl->arena.p);
@@ -1568,9 +1573,18 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
 // kernels, read the nodes' pod slack in 64 bits (node_left, in the place of
 // node_slack) and leave per-block partials that k_shortfall_close closes on
 // the same stream; `out` gets what it gets without `sh`.
+// sr_node_view_pods / sr_node_view_plan are the same call with `view` (`out` and `sh` are then not looked
+// at): the kernels of node_view.hip run in place of the others, no per-query output is staged and nothing comes
+// down; every such pass of one call adds its active pods into the call's totals (view_begin, view_end).
+struct NodeViewCall {
+  sr_node_view_out* out;
+  int32_t per = 0;      // SR_NODE_VIEW_CHUNK
+  int32_t judged = 0;   // active pods of the passes so far
+};
+
 static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
                          sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr,
-                         sr_shortfall_out* sh = nullptr) {
+                         sr_shortfall_out* sh = nullptr, NodeViewCall* view = nullptr) {
   if (n == 0) return SR_OK;
   std::vector<int32_t> off(static_cast<size_t>(n) + 1);
   for (int32_t i = 0; i <= n; ++i) off[i] = i;
@@ -1584,13 +1598,20 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
     ctx->err = err;
     return st;
   }
-  for (int32_t i = 0; i < n; ++i)  // a fallback pod: nothing evaluated
-    sr::clear_slot(out, sh, static_cast<size_t>(slot ? slot[i] : i), static_cast<size_t>(w.n_spot),
-                   w.status_host[i] == SR_CAND_FALLBACK ? 1 : 0);
+  for (int32_t i = 0; i < n; ++i) {  // a fallback pod: nothing evaluated
+    const uint8_t fb = w.status_host[i] == SR_CAND_FALLBACK ? 1 : 0;
+    if (!view) sr::clear_slot(out, sh, static_cast<size_t>(slot ? slot[i] : i), static_cast<size_t>(w.n_spot), fb);
+    else if (view->out->fallback) view->out->fallback[slot ? slot[i] : i] = fb;
+  }
   if (w.pod_src.empty()) return SR_OK;
   sr::ExplainStage& x = ctx->x_stage;
-  st = x.plan(w, ctx->x_enc.node_free, snap, pq, sh != nullptr, out->node_mask != nullptr, sh && sh->node_short,
-              &ctx->err);
+  if (view) {
+    const sr::NodeViewAsk ask{slot, view->per};
+    st = x.plan(w, ctx->x_enc.node_free, snap, pq, true, false, false, &ctx->err, &ask);
+  } else {
+    st = x.plan(w, ctx->x_enc.node_free, snap, pq, sh != nullptr, out->node_mask != nullptr, sh && sh->node_short,
+                &ctx->err);
+  }
   if (st != SR_OK) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
@@ -1600,6 +1621,19 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
   HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().dev_out_bytes));
   x.pack(static_cast<char*>(ctx->hx_in.p));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (view) {  // (the totals were zeroed by view_begin and stay on the device until view_end)
+    if (static_cast<size_t>(w.n_spot) != snap->nodes.size()) {
+      ctx->err = "node view: the encode's spot nodes are not the snapshot's";
+      return SR_ERR_STATE;
+    }
+    sr::ExplainPlanArgs vpa;
+    sr::NodeViewArgs na;
+    x.view_args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p),
+                static_cast<char*>(ctx->x_view.p), &vpa, &na);
+    HIP_TRY(ctx, sr::launch_node_view(vpa, na, ctx->stream));
+    view->judged += x.n_pods();
+    return SR_OK;
+  }
   HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
   sr::ExplainPlanArgs pa;
   sr::ShortfallArgs sa;
@@ -1616,6 +1650,38 @@ static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster*
 }
 
 static bool explain_out_ok(const sr_explain_out* out) { return out && out->feasible && out->first && out->counts; }
+
+static bool view_out_ok(const sr_node_view_out* o) {
+  return o && o->judged && o->admits && o->near && o->refuses && o->sole && o->sole_min && o->sole_at;
+}
+
+// The caller's arrays as of no judged query, and the call's totals zeroed on the stream (once a call).
+static sr_status view_begin(sr_ctx* ctx, const sr_snapshot* snap, NodeViewCall* view, bool device) {
+  const size_t ns = snap->nodes.size();
+  sr::node_view_clear(view->out, ns);
+  if (const char* b = std::getenv("SR_NODE_VIEW_CHUNK")) view->per = std::max(0, std::atoi(b));
+  if (!device || ns == 0) return SR_OK;
+  const size_t bytes = sr::node_view_layout(static_cast<size_t>(sr::node_view_stride(static_cast<int32_t>(ns))), 1).bytes;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the totals of the call before)
+  HIP_TRY(ctx, dev_reserve(ctx->x_view, bytes));
+  HIP_TRY(ctx, host_reserve(ctx->hx_view, bytes));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->x_view.p, 0, bytes, ctx->stream));
+  return SR_OK;
+}
+
+// The totals down in one copy and into the caller's arrays.
+static sr_status view_end(sr_ctx* ctx, const sr_snapshot* snap, NodeViewCall* view) {
+  const size_t ns = snap->nodes.size();
+  *view->out->judged = view->judged;
+  if (view->judged == 0 || ns == 0) return SR_OK;
+  const size_t stride = static_cast<size_t>(sr::node_view_stride(static_cast<int32_t>(ns)));
+  const size_t bytes = sr::node_view_layout(stride, 1).bytes;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_view.p, ctx->x_view.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  sr::node_view_unpack(static_cast<const char*>(ctx->hx_view.p), stride, ns, view->out);
+  return SR_OK;
+}
 
 sr_status sr_explain_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
                           sr_explain_out* out) {
@@ -1665,9 +1731,10 @@ struct OwnExplainOut {
 // other pods: candidates of one encode share the state word's host-port bits,
 // so only an encode of its own tells "outside the encoded set" for certain.
 // (sr_shortfall_plan is this with `sh`)
+// (sr_node_view_plan is this with `view`: the batched pass and every SINGLE candidate add into the same totals)
 static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
                               const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how,
-                              sr_shortfall_out* sh) {
+                              sr_shortfall_out* sh, NodeViewCall* view = nullptr) {
   const int32_t nc = cands->n_cand;
   if (nc > 0 && (!cands->cand_pod_off || !cands->cand_pods || !at_pod)) return SR_ERR_INVALID_ARG;
   if (snap->forked) return SR_ERR_STATE;
@@ -1676,10 +1743,18 @@ static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* 
   sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
   if (st != SR_OK) return st;
   const size_t ns = snap->nodes.size();
-  for (int32_t c = 0; c < nc; ++c)  // not asked: as a fallback pod, but fallback = 0
-    if (pq.how[c] == SR_EXPLAIN_NONE) sr::clear_slot(out, sh, static_cast<size_t>(c), ns, 0);
   const int32_t nb = static_cast<int32_t>(pq.batched.size());
-  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data(), sh);
+  if (view) {
+    bool asked = false;
+    for (int32_t c = 0; c < nc; ++c) asked = asked || pq.how[c] != SR_EXPLAIN_NONE;
+    st = view_begin(ctx, snap, view, asked);
+    if (st != SR_OK) return st;
+    if (view->out->fallback) std::fill_n(view->out->fallback, nc, uint8_t(0));
+  } else {
+    for (int32_t c = 0; c < nc; ++c)  // not asked: as a fallback pod, but fallback = 0
+      if (pq.how[c] == SR_EXPLAIN_NONE) sr::clear_slot(out, sh, static_cast<size_t>(c), ns, 0);
+  }
+  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data(), sh, view);
   if (st != SR_OK) return st;
   if (nb > 1)
     for (int32_t i = 0; i < nb; ++i)
@@ -1693,9 +1768,13 @@ static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* 
     // (node_of_pod may be NULL when no asked candidate has an earlier pod)
     const int32_t* map = node_of_pod ? node_of_pod + (off[c] - off[0]) : nullptr;
     for (int32_t k = 0; k < at_pod[c]; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], map[k]);
-    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c, sh);
+    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c, sh, view);
     const sr_status rv = sr_snapshot_revert(snap);
     if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
+  }
+  if (view) {
+    st = view_end(ctx, snap, view);
+    if (st != SR_OK) return st;
   }
   if (out_how) std::copy(pq.how.begin(), pq.how.end(), out_how);
   return SR_OK;
@@ -1724,6 +1803,23 @@ sr_status sr_shortfall_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
   if (why) return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, why, out_how, out);
   OwnExplainOut own(cands->n_cand);
   return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, &own.out, out_how, out);
+}
+
+sr_status sr_node_view_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
+                            sr_node_view_out* out) {
+  if (!ctx || !snap || !cluster || n < 0 || !view_out_ok(out) || (n > 0 && !pods)) return SR_ERR_INVALID_ARG;
+  NodeViewCall view{out};
+  sr_status st = view_begin(ctx, snap, &view, n > 0);
+  if (st != SR_OK) return st;
+  st = explain(ctx, snap, cluster, pods, n, nullptr, nullptr, nullptr, nullptr, &view);
+  return st != SR_OK ? st : view_end(ctx, snap, &view);
+}
+
+sr_status sr_node_view_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                            const int32_t* at_pod, const int32_t* node_of_pod, sr_node_view_out* out, uint8_t* out_how) {
+  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !view_out_ok(out)) return SR_ERR_INVALID_ARG;
+  NodeViewCall view{out};
+  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, nullptr, out_how, nullptr, &view);
 }
 
 sr_status sr_set_timing(sr_ctx* ctx, int32_t mask) {

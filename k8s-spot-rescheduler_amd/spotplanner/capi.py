@@ -184,6 +184,11 @@ class sr_shortfall_out(_KeepsArrays):
     _fields_ = [("near", P32), ("only_nodes", P32), ("only_min", P64), ("only_at", P32), ("node_short", P64)]
 
 
+class sr_node_view_out(_KeepsArrays):
+    _fields_ = [("judged", P32), ("admits", P32), ("near", P32), ("refuses", P32), ("sole", P32), ("sole_min", P64),
+                ("sole_at", P32), ("fallback", PU8)]
+
+
 # The dimensions of sr_shortfall_out in index order: SHORT_NAMES[d] is SR_SHORT_<name> = d.
 SHORT_NAMES = ["CPU", "MEMORY", "EPHEMERAL", "PODS"]
 assert len(SHORT_NAMES) == SR_SHORT_COUNT  # noqa: F821 (parsed from the header)
@@ -424,6 +429,11 @@ def _declare_planner(lib):
     lib.sr_shortfall_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32,
                                       ctypes.POINTER(sr_explain_out), ctypes.POINTER(sr_shortfall_out), PU8]
     lib.sr_shortfall_plan.restype = S
+    lib.sr_node_view_pods.argtypes = [VP, VP, PC, P32, ctypes.c_int32, ctypes.POINTER(sr_node_view_out)]
+    lib.sr_node_view_pods.restype = S
+    lib.sr_node_view_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32,
+                                      ctypes.POINTER(sr_node_view_out), PU8]
+    lib.sr_node_view_plan.restype = S
     lib.sr_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
     lib.sr_plan.restype = S
     lib.sr_plan_first.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
@@ -459,7 +469,8 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_add_pod", "sr_snapshot_fork", "sr_snapshot_revert", "sr_snapshot_node_state",
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
             "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_explain_pods", "sr_explain_candidate",
-            "sr_explain_plan", "sr_shortfall_pods", "sr_shortfall_plan", "sr_plan", "sr_plan_first", "sr_plan_sequence",
+            "sr_explain_plan", "sr_shortfall_pods", "sr_shortfall_plan", "sr_node_view_pods", "sr_node_view_plan",
+            "sr_plan", "sr_plan_first", "sr_plan_sequence",
             "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",
             "sr_comm_init_shm"]

@@ -531,3 +531,112 @@ def shortfallPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnaps
     return shortfall_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
                                  np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod, node_short,
                                  node_mask)
+
+
+@dataclass
+class NodeViewResult:
+    """sr_node_view_out: what each spot node refuses, over the judged queries (asked, inside the encoded set)."""
+    judged: int            # queries evaluated
+    admits: np.ndarray     # [n_spot] judged queries whose mask on the node is 0
+    near: np.ndarray       # [n_spot] ... for which the node is a near miss
+    refuses: np.ndarray    # [n_spot][SR_WHY_COUNT] ... whose mask on the node holds the bit
+    sole: np.ndarray       # [n_spot][SR_WHY_COUNT] ... whose mask on the node is exactly that bit
+    sole_min: np.ndarray   # [n_spot][SR_SHORT_COUNT] smallest shortfall among the sole-d queries, 0 when none
+    sole_at: np.ndarray    # [n_spot][SR_SHORT_COUNT] lowest query slot attaining it, -1 when none
+    fallback: np.ndarray   # [n] 1: outside the encoded predicate set, counted nowhere
+    how: Optional[np.ndarray] = None  # node_view_plan_arrays: [n] capi.SR_EXPLAIN_* the way each candidate went
+
+    def sole_reasons(self, node: int) -> dict:
+        """{reason name: queries only that reason keeps off the node}, reasons with none left out: the single
+        thing that, put right, frees that many queries there."""
+        return {name: int(k) for name, k in zip(capi.WHY_NAMES, self.sole[node]) if k}
+
+    def closest(self, node: int) -> dict:
+        """{dimension name: (shortfall, query slot)} of the node over the queries short of that dimension alone."""
+        return {name: (int(self.sole_min[node][d]), int(self.sole_at[node][d]))
+                for d, name in enumerate(capi.SHORT_NAMES) if self.sole_at[node][d] >= 0}
+
+
+def _node_view_out(n: int, n_spot: int):
+    m, s = max(n, 1), max(n_spot, 1)
+    judged = np.zeros(1, np.int32)
+    admits = np.zeros(s, np.int32)
+    near = np.zeros(s, np.int32)
+    refuses = np.zeros((s, capi.SR_WHY_COUNT), np.int32)
+    sole = np.zeros((s, capi.SR_WHY_COUNT), np.int32)
+    sole_min = np.zeros((s, capi.SR_SHORT_COUNT), np.int64)
+    sole_at = np.full((s, capi.SR_SHORT_COUNT), -1, np.int32)
+    fallback = np.zeros(m, np.uint8)
+    o = capi.sr_node_view_out(capi.ptr(judged, capi.P32), capi.ptr(admits, capi.P32), capi.ptr(near, capi.P32),
+                              capi.ptr(refuses, capi.P32), capi.ptr(sole, capi.P32), capi.ptr(sole_min, capi.P64),
+                              capi.ptr(sole_at, capi.P32), capi.ptr(fallback, capi.PU8))
+
+    def result():
+        return NodeViewResult(int(judged[0]), admits[:n_spot], near[:n_spot], refuses[:n_spot], sole[:n_spot],
+                              sole_min[:n_spot], sole_at[:n_spot], fallback[:n])
+    return o, result
+
+
+def node_view_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr,
+                     pods: np.ndarray) -> NodeViewResult:
+    """sr_node_view_pods over caller-built arrays: every pod judged against the snapshot as it is, reduced per
+    spot node on the device; a query's slot is its index in `pods`."""
+    lib = predicateChecker.lib
+    pods = np.ascontiguousarray(pods, np.int32)
+    o, result = _node_view_out(len(pods), lib.sr_snapshot_num_nodes(snapshot_handle))
+    st = lib.sr_node_view_pods(predicateChecker.handle, snapshot_handle, cluster_ptr, capi.ptr(pods, capi.P32),
+                               len(pods), ctypes.byref(o))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_node_view_pods: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    return result()
+
+
+def node_view_plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
+                          cand_pods: np.ndarray, at_pod: np.ndarray, node_of_pod: np.ndarray) -> NodeViewResult:
+    """sr_node_view_plan, arguments as explain_plan_arrays: every asked candidate's stop pod in the context of its
+    earlier pods, reduced per spot node; a query's slot is its candidate."""
+    lib = predicateChecker.lib
+    cand_off = np.ascontiguousarray(cand_off, np.int32)
+    cand_pods = np.ascontiguousarray(cand_pods, np.int32)
+    at_pod = np.ascontiguousarray(at_pod, np.int32)
+    if node_of_pod is not None:
+        node_of_pod = np.ascontiguousarray(node_of_pod, np.int32)
+    n = len(cand_off) - 1
+    if len(at_pod) != n:
+        raise ValueError("at_pod needs one entry per candidate")
+    c = capi.sr_candidates(n, capi.ptr(cand_off, capi.P32), capi.ptr(cand_pods, capi.P32), None)
+    o, result = _node_view_out(n, lib.sr_snapshot_num_nodes(snapshot_handle))
+    how = np.zeros(max(n, 1), np.uint8)
+    st = lib.sr_node_view_plan(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                               capi.ptr(at_pod, capi.P32),
+                               capi.ptr(node_of_pod, capi.P32) if node_of_pod is not None else None, ctypes.byref(o),
+                               capi.ptr(how, capi.PU8))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_node_view_plan: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    res = result()
+    res.how = how[:n]
+    return res
+
+
+def nodeViewPods(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                 pods: Sequence[Pod]) -> NodeViewResult:
+    """explainPods from the nodes' side: what each spot node refuses among `pods`."""
+    _check_order(spotSnapshot, nodes)
+    enc = spotSnapshot.encode_pods(list(pods))
+    return node_view_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, np.arange(len(pods), dtype=np.int32))
+
+
+def nodeViewPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                 candidates: Sequence[Sequence[Pod]], plan) -> NodeViewResult:
+    """explainPlan from the nodes' side: what each spot node refuses among the stuck candidates of `plan`."""
+    _check_order(spotSnapshot, nodes)
+    flat = [p for c in candidates for p in c]
+    enc = spotSnapshot.encode_pods(flat)
+    cand_off = np.zeros(len(candidates) + 1, np.int32)
+    cand_off[1:] = np.cumsum([len(c) for c in candidates])
+    return node_view_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
+                                 np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod)

@@ -29,7 +29,13 @@ counts-only calls is the cost of asking "by how much" on top of "why".  `why`
 is checked against the sibling array for array and the reductions against
 numpy over node_mask / node_short.
 
+--node-view times sr_node_view_plan on the tick's stuck candidates beside the one other route to the same
+per-node numbers: sr_shortfall_plan with node_mask and node_short, folded over the candidates with numpy on the
+host.  Both routes must give identical arrays; sr_shortfall_plan counts only is timed too, as the cost of the
+same walk without the [n][n_spot] outputs.
+
   python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan] [--shortfall]
+                                [--node-view]
 """
 import argparse
 import json
@@ -48,7 +54,7 @@ from sequence_ref import from_synth  # noqa: E402
 from spotplanner import capi  # noqa: E402
 from spotplanner.planner import PredicateChecker  # noqa: E402
 from spotplanner.rescheduler import (explain_arrays, explain_candidate_arrays, explain_plan_arrays,  # noqa: E402
-                                     plan_arrays, shortfall_arrays, shortfall_plan_arrays)
+                                     node_view_plan_arrays, plan_arrays, shortfall_arrays, shortfall_plan_arrays)
 from spotplanner.synth import SynthCluster  # noqa: E402
 
 
@@ -215,6 +221,84 @@ def shortfall_mode(args, ck, lib, config):
     return line
 
 
+def numpy_fold(why, short, status):
+    """The per-node arrays of sr_node_view_plan from sr_shortfall_plan's node_mask / node_short, with numpy: the
+    judged candidates (asked, not fallback) folded over axis 0; (shortfall, slot) compared lexicographically."""
+    R = capi.SR_WHY_PODS | capi.SR_WHY_CPU | capi.SR_WHY_MEMORY | capi.SR_WHY_EPHEMERAL
+    bits = (capi.SR_WHY_CPU, capi.SR_WHY_MEMORY, capi.SR_WHY_EPHEMERAL, capi.SR_WHY_PODS)
+    q = np.flatnonzero((np.asarray(status) >= 0) & (why.fallback == 0))
+    m = why.node_mask[q].astype(np.int64)          # [judged][n_spot]
+    s = short.node_short[q]                         # [judged][n_spot][4]
+    n_spot = m.shape[1]
+    out = dict(judged=len(q), admits=(m == 0).sum(0), near=((m != 0) & ((m & ~R) == 0)).sum(0),
+               refuses=np.stack([(m >> r & 1).sum(0) for r in range(capi.SR_WHY_COUNT)], 1),
+               sole=np.stack([(m == 1 << r).sum(0) for r in range(capi.SR_WHY_COUNT)], 1),
+               sole_min=np.zeros((n_spot, 4), np.int64), sole_at=np.full((n_spot, 4), -1, np.int32))
+    big = np.iinfo(np.int64).max
+    for d, bit in enumerate(bits):
+        sole = m == bit
+        if not len(q) or not sole.any():
+            continue
+        # a shortfall is at most INT64_MAX, which a sole query may hold: take the first row attaining the minimum
+        # among the sole rows (the rows are in ascending slot order)
+        v = np.where(sole, s[:, :, d], big)
+        lo = v.min(0)
+        first = np.argmax(sole & (v == lo), 0)
+        has = sole.any(0)
+        out["sole_min"][has, d] = lo[has]
+        out["sole_at"][has, d] = q[first[has]]
+    return out
+
+
+def node_view_mode(args, ck, lib, config):
+    inp = from_synth(SynthCluster(config))
+    h = inp.product_snapshot()
+    off, cp = inp.cand_off, inp.cand_pods
+    try:
+        plan = plan_arrays(ck, h, inp.ptr, off, cp)
+        status, mapping = np.array(plan.status, np.int32), np.array(plan.node_of_pod, np.int32)
+        failing = [c for c in range(len(status)) if status[c] >= 0]
+
+        def view():
+            return node_view_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping)
+
+        def route(fold=True):
+            why, short = shortfall_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping)
+            return numpy_fold(why, short, status) if fold else None
+
+        def counts_only():
+            return shortfall_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping, node_short=False, node_mask=False,
+                                         why=False)
+        res, want = view(), route()
+        same = res.judged == want["judged"] and all(
+            np.array_equal(getattr(res, f), want[f]) for f in ("admits", "near", "refuses", "sole", "sole_min", "sole_at"))
+        n_spot = len(inp.spot)
+        line = dict(config=config, mode="node_view_plan", n_cand=len(status), n_failing=len(failing), n_spot=n_spot,
+                    judged=int(res.judged), pairs=len(failing) * n_spot, reps=args.reps,
+                    both_routes_identical=bool(same),
+                    how={name: int(np.sum(res.how == v)) for name, v in
+                         (("none", capi.SR_EXPLAIN_NONE), ("batched", capi.SR_EXPLAIN_BATCHED),
+                          ("single", capi.SR_EXPLAIN_SINGLE))},
+                    nodes_admitting_none=int(np.sum(res.admits == 0)),
+                    nodes_with_a_sole_reason=int(np.sum(res.sole.sum(1) > 0)),
+                    sole={name: int(k) for name, k in zip(capi.WHY_NAMES, res.sole.sum(0)) if k},
+                    node_mask_and_short_mib=round(len(status) * n_spot * 34 / 2 ** 20, 1),
+                    node_view_download_kib=round(n_spot * 152 / 2 ** 10, 1))
+        del want
+        for name, fn in (("node_view_plan", view), ("shortfall_plan_counts_only", counts_only),
+                         ("shortfall_plan_masks_and_short", lambda: route(False)),
+                         ("shortfall_plan_masks_and_short_numpy_fold", route)):
+            print("# timing " + name, file=sys.stderr, flush=True)
+            m = median_of(fn, args.reps)
+            line.update({"ms_%s_median" % name: m[0], "ms_%s_min" % name: m[1], "ms_%s_max" % name: m[2]})
+        if line["ms_node_view_plan_median"] > 0:
+            line["ratio_fold_route_over_node_view"] = round(
+                line["ms_shortfall_plan_masks_and_short_numpy_fold_median"] / line["ms_node_view_plan_median"], 1)
+    finally:
+        lib.sr_snapshot_destroy(h)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="3")
@@ -224,12 +308,15 @@ def main():
     ap.add_argument("--plan", action="store_true", help="time sr_explain_plan against the per-candidate loop")
     ap.add_argument("--shortfall", action="store_true",
                     help="time sr_shortfall_pods (with --plan: sr_shortfall_plan) beside its explain sibling")
+    ap.add_argument("--node-view", action="store_true",
+                    help="time sr_node_view_plan beside sr_shortfall_plan with node_mask / node_short and a numpy fold")
     args = ap.parse_args()
     ck = PredicateChecker(0)
     lib = capi.load_planner()
     for config in [int(x) for x in args.configs.split(",")]:
-        if args.shortfall or args.plan:
-            text = json.dumps(shortfall_mode(args, ck, lib, config) if args.shortfall
+        if args.node_view or args.shortfall or args.plan:
+            text = json.dumps(node_view_mode(args, ck, lib, config) if args.node_view
+                              else shortfall_mode(args, ck, lib, config) if args.shortfall
                               else plan_mode(args, ck, lib, config))
             print(text, flush=True)
             if args.out:

@@ -199,3 +199,83 @@ sr_status sr_shortfall_plan_view(const sr_cluster* cluster, const sr_snapshot* s
 }
 
 }  // extern "C"
+
+namespace {
+
+// `pods` as shortfall_rows takes them: every judged query folded into every node's row by node_view_fold (the
+// statement the kernels of csrc/node_view.hip follow), the rows through the device's column-major layout
+// (node_view_store) and back into `out` by node_view_unpack, as the planner unpacks the downloaded totals.
+sr_status node_view_rows(const sr_cluster* cluster, const sr_snapshot* snap, const int32_t* pods, int32_t n,
+                         const sr::PlanQueries* pq, const int32_t* slot, sr_node_view_out* out,
+                         std::vector<int32_t>* status) {
+  const size_t ns = snap->nodes.size();
+  sr::node_view_clear(out, ns);
+  std::vector<uint16_t> masks(static_cast<size_t>(n) * ns);
+  std::vector<int64_t> shorts(static_cast<size_t>(n) * ns * SR_SHORT_COUNT);
+  const sr_status st = shortfall_rows(cluster, snap, pods, n, pq, nullptr, masks.data(), shorts.data(), status);
+  if (st != SR_OK) return st;
+  std::vector<sr::NodeViewRow> rows(ns);
+  int32_t judged = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    if ((*status)[i] == SR_CAND_FALLBACK) continue;
+    ++judged;
+    for (size_t node = 0; node < ns; ++node)
+      sr::node_view_fold(masks[i * ns + node], shorts.data() + (i * ns + node) * SR_SHORT_COUNT, slot ? slot[i] : i,
+                         &rows[node]);
+  }
+  const size_t stride = static_cast<size_t>(sr::node_view_stride(static_cast<int32_t>(ns)));
+  const sr::NodeViewLayout l = sr::node_view_layout(stride, 1);
+  std::vector<uint64_t> image(l.bytes / 8);
+  char* base = reinterpret_cast<char*>(image.data());
+  for (size_t node = 0; node < ns; ++node)
+    sr::node_view_store(rows[node], reinterpret_cast<uint64_t*>(base + l.min), reinterpret_cast<int32_t*>(base + l.cnt),
+                        reinterpret_cast<int32_t*>(base + l.at), stride, node);
+  sr::node_view_unpack(base, stride, ns, out);
+  *out->judged = judged;
+  return SR_OK;
+}
+
+bool node_view_out_ok(const sr_node_view_out* o) {
+  return o && o->judged && o->admits && o->near && o->refuses && o->sole && o->sole_min && o->sole_at && o->fallback;
+}
+
+}  // namespace
+
+extern "C" {
+
+// sr_node_view_pods on the host: every array of `out` (fallback [n] included) for `pods` against the snapshot
+// as it is.
+sr_status sr_node_view_pods_view(const sr_cluster* cluster, const sr_snapshot* snap, const int32_t* pods, int32_t n,
+                                 sr_node_view_out* out) {
+  if (!cluster || !snap || n < 0 || (n > 0 && !pods) || !node_view_out_ok(out)) return SR_ERR_INVALID_ARG;
+  std::vector<int32_t> status;
+  const sr_status st = node_view_rows(cluster, snap, pods, n, nullptr, nullptr, out, &status);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < n; ++i) out->fallback[i] = status[i] == SR_CAND_FALLBACK ? 1 : 0;
+  return SR_OK;
+}
+
+// sr_node_view_plan's batched pass on the host: how[n_cand] as sr_explain_plan_view gives it, and `out` over the
+// batched candidates alone, each in the context of its earlier pods, its slot the candidate (a candidate that goes
+// the SINGLE way is not evaluated by the view and counted nowhere).
+sr_status sr_node_view_plan_view(const sr_cluster* cluster, const sr_snapshot* snap, const sr_candidates* cands,
+                                 const int32_t* at_pod, const int32_t* node_of_pod, uint8_t* how, sr_node_view_out* out) {
+  if (!cluster || !snap || !cands || !at_pod || !how || !node_view_out_ok(out)) return SR_ERR_INVALID_ARG;
+  sr::PlanQueries pq;
+  sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
+  if (st != SR_OK) return st;
+  const int32_t nc = cands->n_cand, nb = static_cast<int32_t>(pq.batched.size());
+  std::copy(pq.how.begin(), pq.how.end(), how);
+  std::fill_n(out->fallback, nc, uint8_t(0));
+  std::vector<int32_t> status;
+  st = node_view_rows(cluster, snap, pq.pods.data(), nb, &pq, pq.batched.data(), out, &status);
+  if (st != SR_OK) return st;
+  for (int32_t i = 0; i < nb; ++i) {
+    if (status[i] != SR_CAND_FALLBACK) continue;
+    if (nb > 1) how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
+    else out->fallback[pq.batched[i]] = 1;
+  }
+  return SR_OK;
+}
+
+}  // extern "C"
