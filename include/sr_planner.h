@@ -748,6 +748,57 @@ sr_status sr_node_view_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const
                             const sr_candidates *cands, const int32_t *at_pod, const int32_t *node_of_pod,
                             sr_node_view_out *out, uint8_t *out_how /* optional [n_cand] */);
 
+/* "How far is each stuck candidate from draining": canDrainNode's loop with
+ * the `return err` at the first unplaceable pod (rescheduler.go:359-364)
+ * replaced by "note the pod and go on, state unchanged".  For an asked
+ * candidate with pods p[0..n) in podsForDeletion order, against the snapshot
+ * as it stands:
+ *
+ *   Fork
+ *   for k in 0..n:
+ *     j = first spot position whose predicates pass for p[k]   (findSpotNodeForPod)
+ *     j found:  node_of_pod[k] = j; AddPod(p[k], j)            (:366)
+ *     none:     node_of_pod[k] = -1; p[k] is a blocker; nothing is added
+ *   Revert
+ *
+ * So the first blocker is sr_plan_out.status[c], every pod before it gets
+ * sr_plan_out.node_of_pod, and a candidate sr_plan reports SR_CAND_OK has 0
+ * blockers and the plan's mapping.  With L the candidate's list without the
+ * blockers before blocker k, the counts row of k is sr_explain_candidate's for
+ * (L, L's pods at their positions, at_pod = k's place in L).  ask[c] >= 0 asks
+ * for candidate c (sr_plan_out.status can be passed as it is: OK, EMPTY,
+ * FALLBACK and SKIPPED are negative); a candidate not asked has blockers and
+ * first -1, its pods -1 and zero rows, an asked candidate without pods 0
+ * blockers.  Arrays are indexed by the candidate's local position, node_of_pod
+ * and counts by the pod's place in cand_pods relative to cand_pod_off[0];
+ * cand_global is ignored.  A candidate that is plain as a whole (DESIGN.md
+ * 1.2: no pod changes anything for a later one but its node's pod count and
+ * requested cpu / memory / ephemeral, and it has at most SR_BLOCKERS_BATCH_PODS
+ * pods) is planned by one device pass together with all others of its kind
+ * (SR_EXPLAIN_BATCHED in out_how); every other one pod by pod through Fork /
+ * explain / AddPod / Revert (SR_EXPLAIN_SINGLE).  A candidate one of whose pods
+ * lies outside the encoded predicate set reports fallback = 1, blockers and
+ * first -1 and its pods -1.  With no spot nodes every pod of an asked candidate
+ * is a blocker with a zero counts row (sr_explain_plan gives feasible 0, first
+ * -1 and zero counts there).  SR_ERR_INVALID_ARG: NULL handles or required
+ * outputs, a NULL ask with n_cand > 0, a pod index of an asked candidate out
+ * of range; SR_ERR_STATE on a forked snapshot.  Arguments are checked before
+ * the first Fork and the snapshot is restored on every path; no collective,
+ * and nothing of the planning side is touched, as for sr_explain_plan;
+ * n_cand == 0 is SR_OK. */
+#define SR_BLOCKERS_BATCH_PODS 256
+typedef struct {
+  int32_t *blockers;     /* [n_cand] pods of the candidate that fit nowhere; -1: not asked, or fallback */
+  int32_t *first;        /* [n_cand] index of the first blocker in the candidate's list, -1: none / not asked / fallback */
+  int32_t *node_of_pod;  /* [pods of the list] spot position; -1: blocker, or pod of a candidate not judged */
+  int32_t *counts;       /* optional [pods of the list][SR_WHY_COUNT]: for a blocker, the spot nodes refusing it per
+                            reason in its context (sr_explain_plan's counts); zero rows elsewhere */
+  uint8_t *fallback;     /* optional [n_cand] 1: a pod of the candidate lies outside the encoded set; nothing reported */
+} sr_blockers_out;
+sr_status sr_blockers_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
+                           const sr_candidates *cands, const int32_t *ask /* [n_cand], >= 0: asked */,
+                           sr_blockers_out *out, uint8_t *out_how /* optional [n_cand] SR_EXPLAIN_* */);
+
 /* The planning segment as run() executes it (rescheduler.go:228-287): the
  * candidates in order until the first whose plan succeeds (drain + break,
  * :280-286).  The device plans prefix batches of 16, 32, 64, ... candidates

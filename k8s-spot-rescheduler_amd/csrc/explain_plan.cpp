@@ -7,18 +7,7 @@
 
 namespace sr {
 
-namespace {
-
-// What of a pod can meet the same thing of another pod on one node.
-struct PodTraits {
-  bool ports;    // a host port or an inline disk
-  bool scalars;  // a scalar name or an attachable volume
-  bool anti;     // required anti-affinity (terms or the flag)
-  bool terms;    // ... or required affinity terms
-  bool spread;   // a DoNotSchedule spread constraint
-};
-
-PodTraits traits_of(const sr_cluster* c, int32_t pod) {
+PodTraits pod_traits(const sr_cluster* c, int32_t pod) {
   PodTraits t;
   t.ports = has_ports(c, pod);
   t.scalars = has_scalars(c, pod) || att_count(c, pod) > 0;
@@ -28,10 +17,6 @@ PodTraits traits_of(const sr_cluster* c, int32_t pod) {
   t.spread = has_spread(c, pod);
   return t;
 }
-
-constexpr int64_t kQuantityEnd = int64_t(1) << 62;  // the encoder takes node quantities in [0, 2^62)
-
-}  // namespace
 
 sr_status plan_queries(const sr_snapshot* snap, const sr_cluster* c, const sr_candidates* cands, const int32_t* at_pod,
                        const int32_t* node_of_pod, PlanQueries* out) {
@@ -61,12 +46,12 @@ sr_status plan_queries(const sr_snapshot* snap, const sr_cluster* c, const sr_ca
     if (k < 0) continue;
     const int32_t* pods = cands->cand_pods + off[i];
     const int32_t* map = node_of_pod ? node_of_pod + (off[i] - off[0]) : nullptr;
-    const PodTraits stop = traits_of(c, pods[k]);
+    const PodTraits stop = pod_traits(c, pods[k]);
     // with no earlier pod the context is empty whatever the stop pod carries
     bool plain = k == 0 || !(stop.terms || stop.spread);
     list.clear();
     for (int32_t q = 0; q < k && plain; ++q) {
-      const PodTraits e = traits_of(c, pods[q]);
+      const PodTraits e = pod_traits(c, pods[q]);
       if ((stop.ports && e.ports) || (stop.scalars && e.scalars) || e.anti) plain = false;
       PlanCtxEntry en{map[q], 1, {0, 0, 0}};
       for (int d = 0; d < 3 && plain; ++d) {

@@ -30,6 +30,18 @@ struct PlanCtxEntry {
 };
 static_assert(sizeof(PlanCtxEntry) == 32, "read by the kernel as it stands");
 
+// What of a pod can meet the same thing of another pod on one node.
+struct PodTraits {
+  bool ports;    // a host port or an inline disk
+  bool scalars;  // a scalar name or an attachable volume
+  bool anti;     // required anti-affinity (terms or the flag)
+  bool terms;    // ... or required affinity terms
+  bool spread;   // a DoNotSchedule spread constraint
+};
+PodTraits pod_traits(const sr_cluster* c, int32_t pod);
+
+constexpr int64_t kQuantityEnd = int64_t(1) << 62;  // the encoder takes node quantities in [0, 2^62)
+
 struct PlanQueries {
   std::vector<uint8_t> how;           // [n_cand] SR_EXPLAIN_NONE / BATCHED / SINGLE
   std::vector<int32_t> batched;       // the candidates going the batched way, ascending

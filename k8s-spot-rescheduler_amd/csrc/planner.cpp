@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "blockers_dev.hpp"
 #include "explain_dev.hpp"
 #include "explain_stage.hpp"
 #include "host.hpp"
@@ -216,6 +217,7 @@ struct sr_ctx {
   // allocated anew between the passes)
   DevBuf x_view;
   HostBuf hx_view;
+  sr::BlockersStage b_stage;  // sr_blockers_plan: its batched pass through x_in / x_out (blockers.hpp)
 };
 
 namespace {
@@ -1820,6 +1822,115 @@ sr_status sr_node_view_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
   if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !view_out_ok(out)) return SR_ERR_INVALID_ARG;
   NodeViewCall view{out};
   return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, nullptr, out_how, nullptr, &view);
+}
+
+// sr_blockers_plan's batched pass: the pods of every candidate that is plain as a whole (blockers.hpp), encoded
+// as single-pod candidates by the explain encoder against the snapshot as it is; one upload, one launch of
+// k_blockers (a wave a candidate), one download.  A candidate the encode hands a fallback pod back for leaves
+// the batch (ways->how becomes SINGLE), for the reason given above explain_plan.
+static sr_status blockers_batched(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster,
+                                  const sr_candidates* cands, sr::BlockerWays* ways, sr_blockers_out* out) {
+  std::vector<int32_t> flat;
+  sr::blockers_flat(cands, *ways, &flat);
+  if (flat.empty()) {  // (asked candidates without pods)
+    for (int32_t c : ways->batched) out->blockers[c] = 0;
+    return SR_OK;
+  }
+  const int32_t n = static_cast<int32_t>(flat.size());
+  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
+  for (int32_t i = 0; i <= n; ++i) off[i] = i;
+  const sr_candidates singles{n, off.data(), flat.data(), nullptr};
+  sr::Workload& w = ctx->x_wl;
+  ctx->x_enc.want_why = true;
+  w.reuse.drop();  // always a full encode: the tags belong to it
+  std::string err;
+  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &singles, &w, &err);
+  if (st != SR_OK) {
+    ctx->err = err;
+    return st;
+  }
+  sr::BlockersStage& x = ctx->b_stage;
+  st = x.plan(w, ctx->x_enc.node_free, snap, cluster, cands, ways, out->counts != nullptr, &ctx->err);
+  if (st != SR_OK || x.n_cand() == 0) return st;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
+  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
+  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().out_bytes));
+  x.pack(static_cast<char*>(ctx->hx_in.p));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (x.at().zero_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
+  sr::BlockersArgs ba;
+  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), &ba);
+  HIP_TRY(ctx, sr::launch_blockers(ba, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  x.unpack(static_cast<const char*>(ctx->hx_out.p), cands, out);
+  return SR_OK;
+}
+
+// ... and one SINGLE candidate: the loop of the contract itself, every pod explained alone against the forked
+// snapshot that holds the pods placed before it.
+static sr_status blockers_single(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                                 int32_t c, sr_blockers_out* out) {
+  const int32_t* off = cands->cand_pod_off;
+  const int32_t* pods = cands->cand_pods + off[c];
+  const int32_t np = off[c + 1] - off[c];
+  const size_t p0 = static_cast<size_t>(off[c] - off[0]);
+  sr_status st = sr_snapshot_fork(snap);
+  if (st != SR_OK) return st;
+  OwnExplainOut own(1);
+  uint8_t fb = 0;
+  own.out.fallback = &fb;
+  int32_t blockers = 0, first = -1;
+  for (int32_t k = 0; k < np && st == SR_OK && !fb; ++k) {
+    st = explain(ctx, snap, cluster, pods + k, 1, &own.out);
+    if (st != SR_OK || fb) break;
+    out->node_of_pod[p0 + k] = own.first[0];
+    if (own.first[0] >= 0) {
+      sr::snapshot_add_pod(snap, cluster, pods[k], own.first[0]);
+      continue;
+    }
+    ++blockers;
+    if (first < 0) first = k;
+    if (out->counts) std::copy_n(own.counts.data(), SR_WHY_COUNT, out->counts + (p0 + k) * SR_WHY_COUNT);
+  }
+  const sr_status rv = sr_snapshot_revert(snap);
+  if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
+  if (fb) {
+    sr::blockers_clear(cands, c, 1, out);
+  } else {
+    out->blockers[c] = blockers;
+    out->first[c] = first;
+  }
+  return SR_OK;
+}
+
+sr_status sr_blockers_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
+                           const int32_t* ask, sr_blockers_out* out, uint8_t* out_how) {
+  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !out || !out->blockers || !out->first)
+    return SR_ERR_INVALID_ARG;
+  const int32_t nc = cands->n_cand;
+  if (nc == 0) return SR_OK;
+  if (!cands->cand_pod_off || !ask) return SR_ERR_INVALID_ARG;
+  const int32_t* off = cands->cand_pod_off;
+  if (off[nc] < off[0] || (off[nc] > off[0] && (!cands->cand_pods || !out->node_of_pod))) return SR_ERR_INVALID_ARG;
+  if (snap->forked) return SR_ERR_STATE;
+  // (the ways are decided apart from the context: an argument error returns before the context is looked at)
+  sr::BlockerWays ways;
+  sr_status st = sr::blockers_ways(snap, cluster, cands, ask, &ways);
+  if (st != SR_OK) return st;
+  for (int32_t c = 0; c < nc; ++c) sr::blockers_clear(cands, c, 0, out);
+  st = blockers_batched(ctx, snap, cluster, cands, &ways, out);
+  if (st != SR_OK) return st;
+  for (int32_t c = 0; c < nc; ++c) {
+    if (ways.how[c] != SR_EXPLAIN_SINGLE) continue;
+    st = blockers_single(ctx, snap, cluster, cands, c, out);
+    if (st != SR_OK) return st;
+  }
+  if (out_how) std::copy(ways.how.begin(), ways.how.end(), out_how);
+  return SR_OK;
 }
 
 sr_status sr_set_timing(sr_ctx* ctx, int32_t mask) {

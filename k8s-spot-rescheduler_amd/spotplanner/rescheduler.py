@@ -640,3 +640,71 @@ def nodeViewPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapsh
     cand_off[1:] = np.cumsum([len(c) for c in candidates])
     return node_view_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
                                  np.arange(len(flat), dtype=np.int32), plan.status, plan.node_of_pod)
+
+
+@dataclass
+class BlockersResult:
+    """sr_blockers_out for n candidates: every pod that keeps a stuck candidate from draining."""
+    blockers: np.ndarray      # [n] pods of the candidate that fit nowhere; -1: not asked, or fallback
+    first: np.ndarray         # [n] index of the first blocker in the candidate's list, -1: none
+    node_of_pod: np.ndarray   # [pods of the list] spot position; -1: blocker, or pod of a candidate not judged
+    counts: Optional[np.ndarray]  # [pods of the list][SR_WHY_COUNT] a blocker's refusing nodes per reason, or None
+    fallback: np.ndarray      # [n] 1: a pod of the candidate lies outside the encoded set
+    how: np.ndarray           # [n] capi.SR_EXPLAIN_* the way each candidate went
+    cand_off: np.ndarray      # [n + 1] the candidates' pods in node_of_pod / counts (relative to the first)
+
+    def blocker_pods(self, c: int) -> List[int]:
+        """The indices, in candidate c's list, of its pods that fit nowhere."""
+        if self.blockers[c] < 0:
+            return []
+        row = self.node_of_pod[self.cand_off[c]:self.cand_off[c + 1]]
+        return [int(k) for k in np.nonzero(row < 0)[0]]
+
+    def ranking(self) -> List[int]:
+        """The judged candidates with at least one blocker, fewest blockers first (ties in candidate order):
+        where an operator's effort goes furthest."""
+        stuck = [c for c in range(len(self.blockers)) if self.blockers[c] > 0]
+        return sorted(stuck, key=lambda c: (int(self.blockers[c]), c))
+
+
+def blockers_plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, cand_off: np.ndarray,
+                         cand_pods: np.ndarray, ask: np.ndarray, counts: bool = True) -> BlockersResult:
+    """sr_blockers_plan: canDrainNode's loop without its early return for every candidate with ask[c] >= 0
+    (plan.status as it is asks for the stuck ones)."""
+    lib = predicateChecker.lib
+    cand_off = np.ascontiguousarray(cand_off, np.int32)
+    cand_pods = np.ascontiguousarray(cand_pods, np.int32)
+    ask = np.ascontiguousarray(ask, np.int32)
+    n = len(cand_off) - 1
+    if len(ask) != n:
+        raise ValueError("ask needs one entry per candidate")
+    total = int(cand_off[n] - cand_off[0]) if n > 0 else 0
+    c = capi.sr_candidates(n, capi.ptr(cand_off, capi.P32), capi.ptr(cand_pods, capi.P32), None)
+    blockers = np.full(max(n, 1), -1, np.int32)
+    first = np.full(max(n, 1), -1, np.int32)
+    node_of_pod = np.full(max(total, 1), -1, np.int32)
+    cnt = np.zeros((max(total, 1), capi.SR_WHY_COUNT), np.int32) if counts else None
+    fallback = np.zeros(max(n, 1), np.uint8)
+    how = np.zeros(max(n, 1), np.uint8)
+    o = capi.sr_blockers_out(capi.ptr(blockers, capi.P32), capi.ptr(first, capi.P32), capi.ptr(node_of_pod, capi.P32),
+                             capi.ptr(cnt, capi.P32) if counts else None, capi.ptr(fallback, capi.PU8))
+    st = lib.sr_blockers_plan(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                              capi.ptr(ask, capi.P32), ctypes.byref(o), capi.ptr(how, capi.PU8))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_blockers_plan: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    return BlockersResult(blockers[:n], first[:n], node_of_pod[:total], cnt[:total] if counts else None, fallback[:n],
+                          how[:n], cand_off - cand_off[0] if n > 0 else np.zeros(1, np.int32))
+
+
+def blockersPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                 candidates: Sequence[Sequence[Pod]], plan, counts: bool = True) -> BlockersResult:
+    """Every blocker of every stuck candidate of `plan` (plan_arrays' result for `candidates`), in one call."""
+    _check_order(spotSnapshot, nodes)
+    flat = [p for c in candidates for p in c]
+    enc = spotSnapshot.encode_pods(flat)
+    cand_off = np.zeros(len(candidates) + 1, np.int32)
+    cand_off[1:] = np.cumsum([len(c) for c in candidates])
+    return blockers_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
+                                np.arange(len(flat), dtype=np.int32), plan.status, counts)

@@ -34,8 +34,16 @@ per-node numbers: sr_shortfall_plan with node_mask and node_short, folded over t
 host.  Both routes must give identical arrays; sr_shortfall_plan counts only is timed too, as the cost of the
 same walk without the [n][n_spot] outputs.
 
+--blockers times sr_blockers_plan on the tick's stuck candidates, with and without counts, beside (b) the only
+other route to the same numbers -- the contract's loop on the host through the public calls, Fork, then per pod
+sr_explain_pods of that pod alone and sr_snapshot_add_pod where it has a first node, Revert -- over a sample of
+--sample stuck candidates (evenly spaced), scaled by stuck / sample, and (c) sr_explain_plan counts only, the
+family's yardstick.  The sample's results must equal the call's; the way split and the distribution of blockers
+per stuck candidate are reported, and the call is timed again asking for the batched candidates alone (the
+device pass without the SINGLE candidates' per-pod calls).
+
   python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan] [--shortfall]
-                                [--node-view]
+                                [--node-view] [--blockers [--sample 40]]
 """
 import argparse
 import json
@@ -53,8 +61,8 @@ from oracle_lib import load_oracle  # noqa: E402
 from sequence_ref import from_synth  # noqa: E402
 from spotplanner import capi  # noqa: E402
 from spotplanner.planner import PredicateChecker  # noqa: E402
-from spotplanner.rescheduler import (explain_arrays, explain_candidate_arrays, explain_plan_arrays,  # noqa: E402
-                                     node_view_plan_arrays, plan_arrays, shortfall_arrays, shortfall_plan_arrays)
+from spotplanner.rescheduler import (blockers_plan_arrays, explain_arrays, explain_candidate_arrays,  # noqa: E402
+                                     explain_plan_arrays, node_view_plan_arrays, plan_arrays, shortfall_arrays, shortfall_plan_arrays)
 from spotplanner.synth import SynthCluster  # noqa: E402
 
 
@@ -299,6 +307,74 @@ def node_view_mode(args, ck, lib, config):
     return line
 
 
+def blockers_mode(args, ck, lib, config):
+    inp = from_synth(SynthCluster(config))
+    h = inp.product_snapshot()
+    off, cp = inp.cand_off, inp.cand_pods
+    try:
+        plan = plan_arrays(ck, h, inp.ptr, off, cp)
+        status, mapping = np.array(plan.status, np.int32), np.array(plan.node_of_pod, np.int32)
+        stuck = [c for c in range(len(status)) if status[c] >= 0]
+        step = max(1, len(stuck) // max(1, args.sample))
+        sample = stuck[::step][:args.sample]
+
+        def call(counts=True, ask=None):
+            return blockers_plan_arrays(ck, h, inp.ptr, off, cp, status if ask is None else ask, counts=counts)
+
+        def host_loop():
+            out = {}
+            for c in sample:
+                assert lib.sr_snapshot_fork(h) == capi.SR_OK
+                try:
+                    row, rows = [], []
+                    for p in cp[off[c]:off[c + 1]]:
+                        one = explain_arrays(ck, h, inp.ptr, np.array([p], np.int32), node_mask=False)
+                        row.append(int(one.first[0]))
+                        rows.append(one.counts[0].copy() if one.first[0] < 0 else np.zeros(capi.SR_WHY_COUNT, np.int32))
+                        if one.first[0] >= 0:
+                            lib.sr_snapshot_add_pod(h, inp.ptr, int(p), int(one.first[0]))
+                finally:
+                    assert lib.sr_snapshot_revert(h) == capi.SR_OK
+                out[c] = (row, rows)
+            return out
+
+        def counts_only():
+            return explain_plan_arrays(ck, h, inp.ptr, off, cp, status, mapping, node_mask=False)
+        res, loop = call(), host_loop()
+        rel = off - off[0]
+        same = all(list(res.node_of_pod[rel[c]:rel[c + 1]]) == row and
+                   np.array_equal(res.counts[rel[c]:rel[c + 1]], np.array(rows).reshape(-1, capi.SR_WHY_COUNT))
+                   for c, (row, rows) in loop.items())
+        per = res.blockers[stuck]
+        hist = {str(int(k)): int(v) for k, v in zip(*np.unique(per, return_counts=True))}
+        line = dict(config=config, mode="blockers_plan", n_cand=len(status), n_stuck=len(stuck), n_spot=len(inp.spot),
+                    pods_of_stuck=int(sum(off[c + 1] - off[c] for c in stuck)), reps=args.reps,
+                    how={name: int(np.sum(res.how == v)) for name, v in
+                         (("none", capi.SR_EXPLAIN_NONE), ("batched", capi.SR_EXPLAIN_BATCHED),
+                          ("single", capi.SR_EXPLAIN_SINGLE))},
+                    fallback=int(res.fallback.sum()), first_equals_status=bool(np.array_equal(res.first[stuck], status[stuck])),
+                    blockers_per_stuck_candidate=hist, one_pod_away=int(np.sum(per == 1)),
+                    median_blockers=float(np.median(per)) if len(per) else 0.0, max_blockers=int(per.max()) if len(per) else 0,
+                    sample=len(sample), sample_equals_call=bool(same))
+        only_batched = np.where(res.how == capi.SR_EXPLAIN_BATCHED, status, -1).astype(np.int32)
+        line["pods_of_batched"] = int(sum(off[c + 1] - off[c] for c in stuck if res.how[c] == capi.SR_EXPLAIN_BATCHED))
+        for name, fn in (("blockers_plan", call), ("blockers_plan_without_counts", lambda: call(False)),
+                         ("blockers_plan_batched_candidates_only", lambda: call(True, only_batched)),
+                         ("blockers_plan_batched_candidates_only_without_counts", lambda: call(False, only_batched)),
+                         ("explain_plan_counts_only", counts_only), ("host_loop_sample", host_loop)):
+            print("# timing " + name, file=sys.stderr, flush=True)
+            m = median_of(fn, args.reps if name != "host_loop_sample" else min(args.reps, 3))
+            line.update({"ms_%s_median" % name: m[0], "ms_%s_min" % name: m[1], "ms_%s_max" % name: m[2]})
+        scale = len(stuck) / max(1, len(sample))
+        line["ms_host_loop_scaled_to_all_stuck"] = round(line["ms_host_loop_sample_median"] * scale, 1)
+        if line["ms_blockers_plan_median"] > 0:
+            line["ratio_host_loop_over_blockers_plan"] = round(
+                line["ms_host_loop_scaled_to_all_stuck"] / line["ms_blockers_plan_median"], 1)
+    finally:
+        lib.sr_snapshot_destroy(h)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="3")
@@ -310,12 +386,16 @@ def main():
                     help="time sr_shortfall_pods (with --plan: sr_shortfall_plan) beside its explain sibling")
     ap.add_argument("--node-view", action="store_true",
                     help="time sr_node_view_plan beside sr_shortfall_plan with node_mask / node_short and a numpy fold")
+    ap.add_argument("--blockers", action="store_true",
+                    help="time sr_blockers_plan beside the host loop of its contract and sr_explain_plan counts only")
+    ap.add_argument("--sample", type=int, default=40, help="--blockers: stuck candidates the host loop is timed over")
     args = ap.parse_args()
     ck = PredicateChecker(0)
     lib = capi.load_planner()
     for config in [int(x) for x in args.configs.split(",")]:
-        if args.node_view or args.shortfall or args.plan:
-            text = json.dumps(node_view_mode(args, ck, lib, config) if args.node_view
+        if args.blockers or args.node_view or args.shortfall or args.plan:
+            text = json.dumps(blockers_mode(args, ck, lib, config) if args.blockers
+                              else node_view_mode(args, ck, lib, config) if args.node_view
                               else shortfall_mode(args, ck, lib, config) if args.shortfall
                               else plan_mode(args, ck, lib, config))
             print(text, flush=True)

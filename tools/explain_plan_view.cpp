@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../k8s-spot-rescheduler_amd/csrc/blockers.hpp"
 #include "../k8s-spot-rescheduler_amd/csrc/explain_stage.hpp"
 #include "../k8s-spot-rescheduler_amd/csrc/host.hpp"
 
@@ -275,6 +276,132 @@ sr_status sr_node_view_plan_view(const sr_cluster* cluster, const sr_snapshot* s
     if (nb > 1) how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
     else out->fallback[pq.batched[i]] = 1;
   }
+  return SR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One SINGLE candidate of sr_blockers_plan on the host: the contract's loop, every pod encoded alone against the
+// forked snapshot and judged by explain_node on every node.
+sr_status blockers_single_view(const sr_cluster* cluster, sr_snapshot* snap, const sr_candidates* cands, int32_t c,
+                               sr_blockers_out* out) {
+  const int32_t* off = cands->cand_pod_off;
+  const int32_t* pods = cands->cand_pods + off[c];
+  const int32_t np = off[c + 1] - off[c], ns = static_cast<int32_t>(snap->nodes.size());
+  const size_t p0 = static_cast<size_t>(off[c] - off[0]);
+  sr_status st = sr_snapshot_fork(snap);
+  if (st != SR_OK) return st;
+  int32_t blockers = 0, first = -1;
+  bool fallback = false;
+  for (int32_t k = 0; k < np && st == SR_OK && !fallback; ++k) {
+    const int32_t one_off[2] = {0, 1};
+    const sr_candidates one{1, one_off, pods + k, nullptr};
+    sr::EncoderCache cache;
+    cache.want_why = true;
+    sr::Workload w;
+    std::string err;
+    sr::ExplainPrograms x;
+    std::vector<sr::ExplainPod> xp;
+    st = sr::encode_workload(&cache, snap, cluster, &one, &w, &err);
+    if (st != SR_OK) break;
+    if (w.status_host[0] == SR_CAND_FALLBACK) {
+      fallback = true;
+      break;
+    }
+    if (w.pod_src.size() != 1 || !sr::build_explain(w, &x)) {
+      st = SR_ERR_STATE;
+      break;
+    }
+    sr::explain_pods(w, &xp);
+    int32_t at = -1, row[SR_WHY_COUNT] = {0};
+    for (int32_t node = 0; node < ns; ++node) {
+      const uint32_t m = sr::explain_node(x, xp[0], w.atoms.data(), w.Wp, cache.node_free.data(), w.n_pad, node);
+      if (m == 0 && at < 0) at = node;
+      for (int r = 0; r < SR_WHY_COUNT; ++r) row[r] += m >> r & 1;
+    }
+    out->node_of_pod[p0 + k] = at;
+    if (at >= 0) {
+      sr::snapshot_add_pod(snap, cluster, pods[k], at);
+      continue;
+    }
+    ++blockers;
+    if (first < 0) first = k;
+    if (out->counts) std::copy_n(row, SR_WHY_COUNT, out->counts + (p0 + k) * SR_WHY_COUNT);
+  }
+  const sr_status rv = sr_snapshot_revert(snap);
+  if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
+  if (fallback) {
+    sr::blockers_clear(cands, c, 1, out);
+  } else {
+    out->blockers[c] = blockers;
+    out->first[c] = first;
+  }
+  return SR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// sr_blockers_plan on the host, every output as the planner writes it: the ways (blockers_ways), the batched
+// pass through BlockersStage on heap blocks with blockers_candidate -- the statement the kernel follows -- in
+// the kernel's place, and the SINGLE candidates by the loop above.  The snapshot is forked and reverted.
+sr_status sr_blockers_plan_view(const sr_cluster* cluster, sr_snapshot* snap, const sr_candidates* cands,
+                                const int32_t* ask, sr_blockers_out* out, uint8_t* how) {
+  if (!cluster || !snap || !cands || cands->n_cand < 0 || !out || !out->blockers || !out->first || !how)
+    return SR_ERR_INVALID_ARG;
+  const int32_t nc = cands->n_cand;
+  if (nc == 0) return SR_OK;
+  if (!cands->cand_pod_off || !ask || !out->node_of_pod) return SR_ERR_INVALID_ARG;
+  if (snap->forked) return SR_ERR_STATE;
+  sr::BlockerWays ways;
+  sr_status st = sr::blockers_ways(snap, cluster, cands, ask, &ways);
+  if (st != SR_OK) return st;
+  for (int32_t c = 0; c < nc; ++c) sr::blockers_clear(cands, c, 0, out);
+  std::vector<int32_t> flat;
+  sr::blockers_flat(cands, ways, &flat);
+  if (flat.empty()) {
+    for (int32_t c : ways.batched) out->blockers[c] = 0;
+  } else {
+    const int32_t n = static_cast<int32_t>(flat.size());
+    std::vector<int32_t> off(static_cast<size_t>(n) + 1);
+    for (int32_t i = 0; i <= n; ++i) off[i] = i;
+    const sr_candidates singles{n, off.data(), flat.data(), nullptr};
+    sr::EncoderCache cache;
+    cache.want_why = true;
+    sr::Workload w;
+    std::string err;
+    st = sr::encode_workload(&cache, snap, cluster, &singles, &w, &err);
+    if (st != SR_OK) return st;
+    sr::BlockersStage x;
+    st = x.plan(w, cache.node_free, snap, cluster, cands, &ways, out->counts != nullptr, &err);
+    if (st != SR_OK) return st;
+    if (x.n_cand() > 0) {
+      std::vector<uint64_t> in(x.at().in_bytes / 8 + 1), dev(x.at().out_bytes / 8 + 1, 0xA5A5A5A5A5A5A5A5ull);
+      x.pack(reinterpret_cast<char*>(in.data()));
+      std::fill_n(reinterpret_cast<char*>(dev.data()), x.at().zero_bytes, 0);
+      sr::BlockersArgs b;
+      x.args(reinterpret_cast<const char*>(in.data()), reinterpret_cast<char*>(dev.data()), &b);
+      std::vector<int32_t> slack;
+      sr::node_slack(snap, b.x.n_pad, &slack);
+      for (int32_t c = 0; c < b.n_cand; ++c) {
+        const int32_t p0 = b.cand_off[c];
+        b.blockers[c] = sr::blockers_candidate(x.programs(), b.pods + p0, b.cand_off[c + 1] - p0, b.x.atoms, b.x.Wp,
+                                               b.x.node_free, b.x.n_pad, b.x.n_spot, slack.data(), b.node_of_pod + p0,
+                                               b.counts ? b.counts + static_cast<size_t>(p0) * SR_WHY_COUNT : nullptr,
+                                               b.first + c);
+      }
+      x.unpack(reinterpret_cast<const char*>(dev.data()), cands, out);
+    }
+  }
+  for (int32_t c = 0; c < nc; ++c) {
+    if (ways.how[c] != SR_EXPLAIN_SINGLE) continue;
+    st = blockers_single_view(cluster, snap, cands, c, out);
+    if (st != SR_OK) return st;
+  }
+  std::copy(ways.how.begin(), ways.how.end(), how);
   return SR_OK;
 }
 
