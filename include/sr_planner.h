@@ -518,7 +518,10 @@ const char *sr_build_info(void);
  * changed its layout; sr_explain_plan likewise: one more function;
  * sr_shortfall_pods and sr_shortfall_plan likewise: two functions and one new
  * output struct, sr_shortfall_out; sr_node_view_pods and sr_node_view_plan
- * likewise: two functions and one new output struct, sr_node_view_out). */
+ * likewise: two functions and one new output struct, sr_node_view_out;
+ * sr_blockers_plan likewise: one function and sr_blockers_out;
+ * sr_evacuate_plan likewise: one function, one new output struct,
+ * sr_evacuate_out, and the SR_EVAC_* values). */
 int32_t     sr_abi_version(void);
 
 /* Batched findSpotNodeForPod (rescheduler.go:338-353): for each pod, the first
@@ -798,6 +801,74 @@ typedef struct {
 sr_status sr_blockers_plan(sr_ctx *ctx, sr_snapshot *snap /* restored */, const sr_cluster *cluster,
                            const sr_candidates *cands, const int32_t *ask /* [n_cand], >= 0: asked */,
                            sr_blockers_out *out, uint8_t *out_how /* optional [n_cand] SR_EXPLAIN_* */);
+
+/* "What does a spot reclaim strand": the question of sr_blockers_plan asked of
+ * the spot side.  Scenario s loses the spot positions lost_pos[lost_off[s] ..
+ * lost_off[s + 1]) and moves the pods of candidate s of `scen`, in order (the
+ * caller decides which: typically sr_pods_for_deletion with owner_filter = 0
+ * over the lost nodes, concatenated in NodeInfoArray order; they need not live
+ * on the lost nodes; cand_global is ignored).  With S' the snapshot
+ * sr_snapshot_create would build from the same spot list with the lost
+ * positions left out, the result for s is sr_blockers_plan's loop over its
+ * pods against S', surviving positions reported as positions of the ORIGINAL
+ * list:
+ *
+ *   for k in 0..n:
+ *     j = first surviving spot position whose predicates pass for p[k] against S' + own placements
+ *     j found:  node_of_pod[k] = j; AddPod(p[k], j)
+ *     none:     node_of_pod[k] = -1; p[k] is stranded; state unchanged
+ *
+ * `snap` is never modified (not even forked), and no S' is built: a scenario
+ * is planned by one device pass against the standing snapshot, a block of
+ * waves a scenario, its own placements kept as dense per-node deltas.  That is
+ * exact only where the standing snapshot says about every surviving node what
+ * S' says and the moved pods meet each other through nothing but arithmetic
+ * (DESIGN.md 1.3); the rule is syntactic and conservative, and decided from
+ * the sr_cluster tables and the snapshot alone:
+ *   no moved pod has required anti-affinity (terms or the flag), affinity
+ *   terms or a DoNotSchedule spread constraint (the first pod included: the
+ *   standing snapshot still counts the lost nodes' pods);
+ *   at most one moved pod has host ports or inline disks, at most one scalars
+ *   or attachable volumes;
+ *   every accounted request is non-negative, and the largest Requested of any
+ *   spot node plus the scenario's total stays below 2^62 per dimension;
+ *   no pod held on a lost node carries required anti-affinity (or scalar
+ *   requests the snapshot could not read).
+ * There is no limit on the pod count.  how[s]: SR_EVAC_JUDGED, the scenario
+ * was planned; SR_EVAC_FALLBACK, a pod lies outside the encoded predicate set
+ * (the meaning `fallback` has everywhere else); SR_EVAC_NOT_PLAIN, the
+ * scenario is outside the rule and NOTHING is reported for it: the caller
+ * (the shim) answers such a scenario by building S' itself
+ * with sr_snapshot_create and calling sr_blockers_plan on it.  For a scenario
+ * not judged stranded and first are -1, its pods -1 and its rows zero.
+ * An empty lost set is allowed (sr_blockers_plan's loop on the snapshot as it
+ * is); with every position lost every pod is stranded with a zero row; a
+ * scenario without pods reports 0 stranded; n_cand == 0 is SR_OK.  Arrays are
+ * indexed by scenario, node_of_pod and counts by the pod's place in cand_pods
+ * relative to cand_pod_off[0].  SR_ERR_INVALID_ARG: NULL handles or required
+ * outputs, a malformed CSR, a lost position outside [0, n_spot) or repeated
+ * within a scenario, a pod index out of range; SR_ERR_STATE on a forked
+ * snapshot, or when the pool has more than 262,144 spot nodes (the lost set is
+ * a bitmask of at most 4,096 row words in a block's LDS).  Arguments are checked before any work; no collective, and nothing
+ * of the planning side is touched, as for sr_explain_plan.  The environment
+ * variables SR_EVAC_GRID (blocks, 1 to 2048) and SR_EVAC_WAVES (waves a block, 1 to
+ * 16), read per call, override the launch shape; results do not depend on
+ * them. */
+#define SR_EVAC_JUDGED 1
+#define SR_EVAC_FALLBACK 2
+#define SR_EVAC_NOT_PLAIN 3
+typedef struct {
+  int32_t *stranded;     /* [n_cand] pods of the scenario that fit nowhere; -1: not judged */
+  int32_t *first;        /* [n_cand] index of the first stranded pod in the scenario's list, -1: none / not judged */
+  int32_t *node_of_pod;  /* [pods of the list] position in the original spot list; -1: stranded, or not judged */
+  int32_t *counts;       /* optional [pods of the list][SR_WHY_COUNT]: for a stranded pod, the SURVIVING nodes refusing
+                            it per reason in its context; zero rows elsewhere */
+  uint8_t *how;          /* optional [n_cand] SR_EVAC_* */
+} sr_evacuate_out;
+sr_status sr_evacuate_plan(sr_ctx *ctx, const sr_snapshot *snap /* not modified */, const sr_cluster *cluster,
+                           const sr_candidates *scen /* scenario s: the pods to re-place, in order */,
+                           const int32_t *lost_off, const int32_t *lost_pos /* CSR [n_cand + 1]: spot positions lost in s */,
+                           sr_evacuate_out *out);
 
 /* The planning segment as run() executes it (rescheduler.go:228-287): the
  * candidates in order until the first whose plan succeeds (drain + break,

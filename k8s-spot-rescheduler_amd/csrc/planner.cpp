@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "blockers_dev.hpp"
+#include "evacuate_dev.hpp"
 #include "explain_dev.hpp"
 #include "explain_stage.hpp"
 #include "host.hpp"
@@ -218,6 +219,12 @@ struct sr_ctx {
   DevBuf x_view;
   HostBuf hx_view;
   sr::BlockersStage b_stage;  // sr_blockers_plan: its batched pass through x_in / x_out (blockers.hpp)
+  // sr_evacuate_plan: its passes through x_in / x_out (evacuate.hpp), and the blocks' dense per-node deltas.
+  // The scratch is zero between launches -- every block restores its slice -- so it is zeroed on the stream
+  // only when it was allocated anew, or when a call ended before its launch was known to have finished
+  sr::EvacuateStage e_stage;
+  DevBuf e_scratch;
+  bool e_scratch_zero = false;
 };
 
 namespace {
@@ -1169,7 +1176,7 @@ void sr_destroy(sr_ctx* ctx) {
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
                     &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off, &ctx->pdb_need, &ctx->pdb_remaining,
-                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out, &ctx->x_view})
+                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out, &ctx->x_view, &ctx->e_scratch})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1930,6 +1937,101 @@ sr_status sr_blockers_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* clu
     if (st != SR_OK) return st;
   }
   if (out_how) std::copy(ways.how.begin(), ways.how.end(), out_how);
+  return SR_OK;
+}
+
+// One pass of sr_evacuate_plan over the scenarios `ids` (all JUDGED by the rule): their pods encoded as
+// single-pod candidates by the explain encoder against the standing snapshot; one upload, one launch of
+// k_evacuate (a block of waves a scenario, grid-stride), one download.  A scenario the encode hands a fallback
+// pod back for is not planned and appended to *fell.
+static sr_status evacuate_pass(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* scen,
+                               const int32_t* lost_off, const int32_t* lost_pos, const std::vector<int32_t>& ids,
+                               std::vector<int32_t>* fell, sr_evacuate_out* out) {
+  std::vector<int32_t> flat;
+  sr::evacuate_flat(scen, ids, &flat);
+  if (flat.empty()) {  // (scenarios without pods)
+    for (int32_t s : ids) {
+      out->stranded[s] = 0;
+      if (out->how) out->how[s] = SR_EVAC_JUDGED;
+    }
+    return SR_OK;
+  }
+  const int32_t n = static_cast<int32_t>(flat.size());
+  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
+  for (int32_t i = 0; i <= n; ++i) off[i] = i;
+  const sr_candidates singles{n, off.data(), flat.data(), nullptr};
+  sr::Workload& w = ctx->x_wl;
+  ctx->x_enc.want_why = true;
+  w.reuse.drop();  // always a full encode: the tags belong to it
+  std::string err;
+  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &singles, &w, &err);
+  if (st != SR_OK) {
+    ctx->err = err;
+    return st;
+  }
+  sr::EvacuateStage& x = ctx->e_stage;
+  st = x.plan(w, ctx->x_enc.node_free, snap, cluster, scen, lost_off, lost_pos, ids, out->counts != nullptr, fell,
+              &ctx->err);
+  if (st != SR_OK || x.n_scen() == 0) return st;
+  int32_t blocks = 0, waves = 0;
+  sr::evacuate_shape(x.n_scen(), std::getenv("SR_EVAC_GRID"), std::getenv("SR_EVAC_WAVES"), &blocks, &waves);
+  const sr::EvacuateScratch sc = sr::evacuate_scratch(x.n_pad(), blocks);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
+  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
+  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
+  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().out_bytes));
+  if (sc.bytes > ctx->e_scratch.cap) ctx->e_scratch_zero = false;
+  HIP_TRY(ctx, dev_reserve(ctx->e_scratch, sc.bytes));
+  if (!ctx->e_scratch_zero && ctx->e_scratch.p)
+    HIP_TRY(ctx, hipMemsetAsync(ctx->e_scratch.p, 0, ctx->e_scratch.cap, ctx->stream));
+  ctx->e_scratch_zero = false;  // until the launch is known to have finished
+  x.pack(static_cast<char*>(ctx->hx_in.p));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (x.at().zero_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
+  sr::EvacuateArgs ea;
+  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), static_cast<char*>(ctx->e_scratch.p),
+         blocks, waves, &ea);
+  HIP_TRY(ctx, sr::launch_evacuate(ea, blocks, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->e_scratch_zero = true;
+  x.unpack(static_cast<const char*>(ctx->hx_out.p), scen, out);
+  return SR_OK;
+}
+
+sr_status sr_evacuate_plan(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* scen,
+                           const int32_t* lost_off, const int32_t* lost_pos, sr_evacuate_out* out) {
+  if (!ctx || !snap || !cluster || !scen || scen->n_cand < 0 || !out || !out->stranded || !out->first)
+    return SR_ERR_INVALID_ARG;
+  const int32_t nc = scen->n_cand;
+  if (nc == 0) return SR_OK;
+  if (!scen->cand_pod_off || !lost_off) return SR_ERR_INVALID_ARG;
+  const int32_t* off = scen->cand_pod_off;
+  if (off[nc] < off[0] || (off[nc] > off[0] && (!scen->cand_pods || !out->node_of_pod))) return SR_ERR_INVALID_ARG;
+  if (lost_off[nc] < lost_off[0] || (lost_off[nc] > lost_off[0] && !lost_pos)) return SR_ERR_INVALID_ARG;
+  if (snap->forked) return SR_ERR_STATE;
+  // (the rule is decided apart from the context: an argument error returns before the context is looked at)
+  sr::EvacuateWays ways;
+  sr_status st = sr::evacuate_ways(snap, cluster, scen, lost_off, lost_pos, &ways);
+  if (st != SR_OK) return st;
+  for (int32_t s = 0; s < nc; ++s) sr::evacuate_clear(scen, s, ways.how[s], out);
+  std::vector<int32_t> fell;
+  st = evacuate_pass(ctx, snap, cluster, scen, lost_off, lost_pos, ways.judged, &fell, out);
+  if (st != SR_OK) return st;
+  // candidates of one encode share the state word's host-port bits (see explain_plan): a scenario the shared
+  // encode handed a fallback pod back for is asked again alone before SR_EVAC_FALLBACK stands
+  for (int32_t s : fell) {
+    std::vector<int32_t> again;
+    if (ways.judged.size() > 1) {
+      st = evacuate_pass(ctx, snap, cluster, scen, lost_off, lost_pos, std::vector<int32_t>{s}, &again, out);
+      if (st != SR_OK) return st;
+    } else {
+      again.push_back(s);
+    }
+    if (!again.empty()) sr::evacuate_clear(scen, s, SR_EVAC_FALLBACK, out);
+  }
   return SR_OK;
 }
 

@@ -193,6 +193,10 @@ class sr_blockers_out(_KeepsArrays):
     _fields_ = [("blockers", P32), ("first", P32), ("node_of_pod", P32), ("counts", P32), ("fallback", PU8)]
 
 
+class sr_evacuate_out(_KeepsArrays):
+    _fields_ = [("stranded", P32), ("first", P32), ("node_of_pod", P32), ("counts", P32), ("how", PU8)]
+
+
 # The dimensions of sr_shortfall_out in index order: SHORT_NAMES[d] is SR_SHORT_<name> = d.
 SHORT_NAMES = ["CPU", "MEMORY", "EPHEMERAL", "PODS"]
 assert len(SHORT_NAMES) == SR_SHORT_COUNT  # noqa: F821 (parsed from the header)
@@ -441,6 +445,9 @@ def _declare_planner(lib):
     lib.sr_blockers_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32,
                                      ctypes.POINTER(sr_blockers_out), PU8]
     lib.sr_blockers_plan.restype = S
+    lib.sr_evacuate_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), P32, P32,
+                                     ctypes.POINTER(sr_evacuate_out)]
+    lib.sr_evacuate_plan.restype = S
     lib.sr_plan.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
     lib.sr_plan.restype = S
     lib.sr_plan_first.argtypes = [VP, VP, PC, ctypes.POINTER(sr_candidates), ctypes.POINTER(sr_plan_out)]
@@ -477,7 +484,7 @@ EXPORTED = ["sr_new_node_map", "sr_node_map_cache_create", "sr_node_map_cache_de
             "sr_snapshot_num_nodes", "sr_create", "sr_destroy", "sr_last_error", "sr_build_info",
             "sr_abi_version", "sr_find_spot_nodes", "sr_can_drain_node", "sr_explain_pods", "sr_explain_candidate",
             "sr_explain_plan", "sr_shortfall_pods", "sr_shortfall_plan", "sr_node_view_pods", "sr_node_view_plan",
-            "sr_blockers_plan",
+            "sr_blockers_plan", "sr_evacuate_plan",
             "sr_plan", "sr_plan_first", "sr_plan_sequence",
             "sr_plan_sequence_pdb", "sr_plan_prepare", "sr_plan_run",
             "sr_set_timing", "sr_get_timing", "sr_comm_unique_id", "sr_comm_init", "sr_comm_init_host",

@@ -708,3 +708,106 @@ def blockersPlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapsh
     cand_off[1:] = np.cumsum([len(c) for c in candidates])
     return blockers_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, cand_off,
                                 np.arange(len(flat), dtype=np.int32), plan.status, counts)
+
+
+@dataclass
+class EvacuateResult:
+    """sr_evacuate_out for n scenarios: what losing each scenario's spot nodes strands."""
+    stranded: np.ndarray      # [n] pods of the scenario that fit on no surviving node; -1: not judged
+    first: np.ndarray         # [n] index of the first stranded pod in the scenario's list, -1: none / not judged
+    node_of_pod: np.ndarray   # [pods of the list] position in the original spot list; -1: stranded, or not judged
+    counts: Optional[np.ndarray]  # [pods of the list][SR_WHY_COUNT] a stranded pod's refusing surviving nodes, or None
+    how: np.ndarray           # [n] capi.SR_EVAC_JUDGED / SR_EVAC_FALLBACK / SR_EVAC_NOT_PLAIN
+    scen_off: np.ndarray      # [n + 1] the scenarios' pods in node_of_pod / counts (relative to the first)
+
+    def stranded_pods(self, s: int) -> List[int]:
+        """The indices, in scenario s's list, of its pods that fit nowhere."""
+        if self.stranded[s] < 0:
+            return []
+        row = self.node_of_pod[self.scen_off[s]:self.scen_off[s + 1]]
+        return [int(k) for k in np.nonzero(row < 0)[0]]
+
+    def ranking(self) -> List[int]:
+        """The judged scenarios that strand at least one pod, most stranded pods first (ties in scenario
+        order): the reclaims that hurt most."""
+        hit = [s for s in range(len(self.stranded)) if self.stranded[s] > 0]
+        return sorted(hit, key=lambda s: (-int(self.stranded[s]), s))
+
+    def not_answered(self) -> List[int]:
+        """The scenarios the call reports nothing for (NOT_PLAIN or FALLBACK): the caller answers them by
+        building the reduced snapshot and calling blockers_plan_arrays on it."""
+        return [s for s in range(len(self.how)) if self.how[s] != capi.SR_EVAC_JUDGED]
+
+
+def evacuate_plan_arrays(predicateChecker: PredicateChecker, snapshot_handle, cluster_ptr, scen_off: np.ndarray,
+                         scen_pods: np.ndarray, lost_off: np.ndarray, lost_pos: np.ndarray,
+                         counts: bool = True) -> EvacuateResult:
+    """sr_evacuate_plan: scenario s loses the spot positions lost_pos[lost_off[s]:lost_off[s + 1]] and re-places
+    the pods scen_pods[scen_off[s]:scen_off[s + 1]], in order, on the surviving nodes."""
+    lib = predicateChecker.lib
+    scen_off = np.ascontiguousarray(scen_off, np.int32)
+    scen_pods = np.ascontiguousarray(scen_pods, np.int32)
+    lost_off = np.ascontiguousarray(lost_off, np.int32)
+    lost_pos = np.ascontiguousarray(lost_pos, np.int32)
+    n = len(scen_off) - 1
+    if len(lost_off) != n + 1:
+        raise ValueError("lost_off needs one entry per scenario and one more")
+    total = int(scen_off[n] - scen_off[0]) if n > 0 else 0
+    c = capi.sr_candidates(n, capi.ptr(scen_off, capi.P32), capi.ptr(scen_pods, capi.P32), None)
+    stranded = np.full(max(n, 1), -1, np.int32)
+    first = np.full(max(n, 1), -1, np.int32)
+    node_of_pod = np.full(max(total, 1), -1, np.int32)
+    cnt = np.zeros((max(total, 1), capi.SR_WHY_COUNT), np.int32) if counts else None
+    how = np.zeros(max(n, 1), np.uint8)
+    o = capi.sr_evacuate_out(capi.ptr(stranded, capi.P32), capi.ptr(first, capi.P32), capi.ptr(node_of_pod, capi.P32),
+                             capi.ptr(cnt, capi.P32) if counts else None, capi.ptr(how, capi.PU8))
+    st = lib.sr_evacuate_plan(predicateChecker.handle, snapshot_handle, cluster_ptr, ctypes.byref(c),
+                              capi.ptr(lost_off, capi.P32), capi.ptr(lost_pos, capi.P32), ctypes.byref(o))
+    if st != capi.SR_OK:
+        err = PlannerError("sr_evacuate_plan: %d %s" % (st, predicateChecker.last_error()))
+        err.status = st
+        raise err
+    return EvacuateResult(stranded[:n], first[:n], node_of_pod[:total], cnt[:total] if counts else None, how[:n],
+                          scen_off - scen_off[0] if n > 0 else np.zeros(1, np.int32))
+
+
+def evacuation_scenarios(nodes, pool_key: Optional[str] = None):
+    """The reclaims worth asking about, as (names, lost sets of spot positions): every spot node lost alone
+    ("node:<name>"), then, with `pool_key`, every set of nodes sharing a value of that node label
+    ("pool:<value>", in order of first appearance; a node without the label is in no pool)."""
+    names, lost = [], []
+    for i, info in enumerate(nodes):
+        names.append("node:" + info.Node.name)
+        lost.append([i])
+    if pool_key is not None:
+        pools = {}
+        for i, info in enumerate(nodes):
+            v = (info.Node.labels or {}).get(pool_key)
+            if v is not None:
+                pools.setdefault(v, []).append(i)
+        for v, members in pools.items():
+            names.append("pool:" + v)
+            lost.append(members)
+    return names, lost
+
+
+def evacuatePlan(predicateChecker: PredicateChecker, spotSnapshot: ClusterSnapshot, nodes,
+                 lost: Sequence[Sequence[int]], moved: Optional[Sequence[Sequence[Pod]]] = None,
+                 counts: bool = True) -> EvacuateResult:
+    """What each reclaim strands: scenario s loses the spot positions lost[s] of `nodes` (evacuation_scenarios
+    builds the usual ones) and re-places moved[s] -- by default every pod of the lost nodes, in NodeInfoArray
+    order -- on the nodes that survive."""
+    _check_order(spotSnapshot, nodes)
+    if moved is None:
+        moved = [[p for i in sorted(set(s)) for p in nodes[i].Pods] for s in lost]
+    if len(moved) != len(lost):
+        raise ValueError("moved needs one pod list per scenario")
+    flat = [p for m in moved for p in m]
+    enc = spotSnapshot.encode_pods(flat)
+    scen_off = np.zeros(len(lost) + 1, np.int32)
+    scen_off[1:] = np.cumsum([len(m) for m in moved])
+    lost_off = np.zeros(len(lost) + 1, np.int32)
+    lost_off[1:] = np.cumsum([len(s) for s in lost])
+    lost_pos = np.array([int(i) for s in lost for i in s], np.int32)
+    return evacuate_plan_arrays(predicateChecker, spotSnapshot.handle, enc.ptr, scen_off,
+                                np.arange(len(flat), dtype=np.int32), lost_off, lost_pos, counts)

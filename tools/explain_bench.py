@@ -42,10 +42,19 @@ family's yardstick.  The sample's results must equal the call's; the way split a
 per stuck candidate are reported, and the call is timed again asking for the batched candidates alone (the
 device pass without the SINGLE candidates' per-pod calls).
 
+--evacuate times sr_evacuate_plan on two workloads over the config's spot pool -- every spot node lost alone, and
+ten pools (position j belongs to pool j % 10, the stand-in for an instance-type-in-a-zone label) -- each scenario
+moving the pods of its lost nodes (DaemonSet and mirror pods left out), with and without counts, beside the only
+other route to the same answer: sr_snapshot_create without the lost nodes, then sr_blockers_plan over the same
+pods, over an evenly spaced sample of --sample scenarios scaled by scenarios / sample.  The sample's rows must
+equal the call's; how many scenarios are JUDGED, NOT_PLAIN and FALLBACK is reported (--variant realistic: the
+config with StatefulSet volumes, init containers and GPU pods).
+
   python tools/explain_bench.py [--configs 3] [--reps 9] [--no-oracle] [--out FILE] [--plan] [--shortfall]
-                                [--node-view] [--blockers [--sample 40]]
+                                [--node-view] [--blockers [--sample 40]] [--evacuate [--variant realistic]]
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -61,9 +70,9 @@ from oracle_lib import load_oracle  # noqa: E402
 from sequence_ref import from_synth  # noqa: E402
 from spotplanner import capi  # noqa: E402
 from spotplanner.planner import PredicateChecker  # noqa: E402
-from spotplanner.rescheduler import (blockers_plan_arrays, explain_arrays, explain_candidate_arrays,  # noqa: E402
-                                     explain_plan_arrays, node_view_plan_arrays, plan_arrays, shortfall_arrays, shortfall_plan_arrays)
-from spotplanner.synth import SynthCluster  # noqa: E402
+from spotplanner.rescheduler import (blockers_plan_arrays, evacuate_plan_arrays, explain_arrays,  # noqa: E402
+                                     explain_candidate_arrays, explain_plan_arrays, node_view_plan_arrays, plan_arrays, shortfall_arrays, shortfall_plan_arrays)
+from spotplanner.synth import AFFINITY, REALISTIC, SynthCluster  # noqa: E402
 
 
 def timed(fn):
@@ -375,6 +384,86 @@ def blockers_mode(args, ck, lib, config):
     return line
 
 
+def evacuate_mode(args, ck, lib, config):
+    kw = {"realistic": REALISTIC, "affinity": AFFINITY}.get(args.variant, {})
+    synth = SynthCluster(config, **kw)
+    inp = from_synth(synth)
+    h = inp.product_snapshot()
+    n_spot = len(inp.spot)
+    flags = synth.pod_flags()
+    skip = capi.SR_POD_MIRROR | capi.SR_POD_DAEMONSET_CONTROLLER
+    held = [[int(p) for p in inp.node_pod_idx[inp.node_pod_off[v]:inp.node_pod_off[v + 1]] if not flags[p] & skip]
+            for v in inp.spot]
+
+    def arrays(lost_sets):
+        scen_off, pods, lost_off, lost_pos = [0], [], [0], []
+        for lost in lost_sets:
+            for j in lost:
+                pods.extend(held[j])
+            scen_off.append(len(pods))
+            lost_pos.extend(lost)
+            lost_off.append(len(lost_pos))
+        return (np.array(scen_off, np.int32), np.array(pods, np.int32), np.array(lost_off, np.int32),
+                np.array(lost_pos, np.int32))
+    line = dict(config=config, variant=args.variant, mode="evacuate_plan", n_spot=n_spot, reps=args.reps,
+                spot_pods_moved=int(sum(len(x) for x in held)))
+    try:
+        for name, lost_sets in (("n_minus_one", [[j] for j in range(n_spot)]),
+                                ("ten_pools", [list(range(r, n_spot, 10)) for r in range(10)])):
+            a = arrays(lost_sets)
+            n = len(lost_sets)
+
+            def call(counts=True):
+                return evacuate_plan_arrays(ck, h, inp.ptr, *a, counts=counts)
+            res = call()
+            judged = [s for s in range(n) if res.how[s] == capi.SR_EVAC_JUDGED]
+            step = max(1, len(judged) // max(1, args.sample))
+            sample = judged[::step][:args.sample]
+
+            def other_route():
+                out = {}
+                for s in sample:
+                    keep = np.setdiff1d(np.arange(n_spot), lost_sets[s]).astype(np.int32)
+                    spot = np.ascontiguousarray(inp.spot[keep], np.int32)
+                    h2 = ctypes.c_void_p()
+                    assert lib.sr_snapshot_create(inp.ptr, capi.ptr(spot, capi.P32), len(spot),
+                                                  capi.ptr(inp.node_pod_off, capi.P32), capi.ptr(inp.node_pod_idx, capi.P32),
+                                                  ctypes.byref(h2)) == capi.SR_OK
+                    try:
+                        pods = a[1][a[0][s]:a[0][s + 1]]
+                        b = blockers_plan_arrays(ck, h2, inp.ptr, np.array([0, len(pods)], np.int32), pods,
+                                                 np.zeros(1, np.int32))
+                    finally:
+                        lib.sr_snapshot_destroy(h2)
+                    out[s] = (np.where(b.node_of_pod >= 0, keep[np.maximum(b.node_of_pod, 0)], -1), b.counts.copy(),
+                              int(b.blockers[0]), int(b.fallback[0]))
+                return out
+            route = other_route()
+            same = all(not fb and np.array_equal(res.node_of_pod[a[0][s]:a[0][s + 1]], row) and res.stranded[s] == k and
+                       np.array_equal(res.counts[a[0][s]:a[0][s + 1]], cnt) for s, (row, cnt, k, fb) in route.items())
+            d = dict(scenarios=n, pods=int(a[0][-1]), judged=len(judged),
+                     not_plain=int(np.sum(res.how == capi.SR_EVAC_NOT_PLAIN)),
+                     fallback=int(np.sum(res.how == capi.SR_EVAC_FALLBACK)),
+                     scenarios_stranding=int(np.sum(res.stranded > 0)),
+                     stranded_pods=int(res.stranded[res.stranded > 0].sum()),
+                     worst=[int(s) for s in res.ranking()[:3]], sample=len(sample), sample_equals_call=bool(same))
+            for label, fn in (("evacuate_plan", call), ("evacuate_plan_without_counts", lambda: call(False)),
+                              ("other_route_sample", other_route)):
+                print("# timing %s %s" % (name, label), file=sys.stderr, flush=True)
+                m = median_of(fn, args.reps if label != "other_route_sample" else min(args.reps, 3))
+                d.update({"ms_%s_median" % label: m[0], "ms_%s_min" % label: m[1], "ms_%s_max" % label: m[2]})
+            d["ms_other_route_scaled_to_judged"] = round(d["ms_other_route_sample_median"] * len(judged) / max(1, len(sample)), 1)
+            if d["ms_evacuate_plan_median"] > 0:
+                d["ratio_other_route_over_evacuate_plan"] = round(d["ms_other_route_scaled_to_judged"] / d["ms_evacuate_plan_median"], 1)
+            line[name] = d
+            if not same:  # a number whose rows differ from the other route's is not published
+                print(json.dumps(line), flush=True)
+                raise SystemExit("evacuate: the other route's rows differ from the call's (%s)" % name)
+    finally:
+        lib.sr_snapshot_destroy(h)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="3")
@@ -388,13 +477,19 @@ def main():
                     help="time sr_node_view_plan beside sr_shortfall_plan with node_mask / node_short and a numpy fold")
     ap.add_argument("--blockers", action="store_true",
                     help="time sr_blockers_plan beside the host loop of its contract and sr_explain_plan counts only")
-    ap.add_argument("--sample", type=int, default=40, help="--blockers: stuck candidates the host loop is timed over")
+    ap.add_argument("--sample", type=int, default=40,
+                    help="--blockers: stuck candidates the host loop is timed over; --evacuate: scenarios of the other route")
+    ap.add_argument("--evacuate", action="store_true",
+                    help="time sr_evacuate_plan (every spot node lost alone; ten pools) beside sr_snapshot_create + sr_blockers_plan")
+    ap.add_argument("--variant", default="baseline", choices=["baseline", "realistic", "affinity"],
+                    help="--evacuate: the synthetic config's variant (bench.py's)")
     args = ap.parse_args()
     ck = PredicateChecker(0)
     lib = capi.load_planner()
     for config in [int(x) for x in args.configs.split(",")]:
-        if args.blockers or args.node_view or args.shortfall or args.plan:
-            text = json.dumps(blockers_mode(args, ck, lib, config) if args.blockers
+        if args.evacuate or args.blockers or args.node_view or args.shortfall or args.plan:
+            text = json.dumps(evacuate_mode(args, ck, lib, config) if args.evacuate
+                              else blockers_mode(args, ck, lib, config) if args.blockers
                               else node_view_mode(args, ck, lib, config) if args.node_view
                               else shortfall_mode(args, ck, lib, config) if args.shortfall
                               else plan_mode(args, ck, lib, config))
