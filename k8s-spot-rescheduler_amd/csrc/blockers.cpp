@@ -2,8 +2,6 @@
 #include "blockers.hpp"
 
 #include <algorithm>
-#include <cstring>
-
 #include "host.hpp"
 
 namespace sr {
@@ -97,137 +95,135 @@ void blockers_clear(const sr_candidates* cands, int32_t c, uint8_t fallback, sr_
   if (out->fallback) out->fallback[c] = fallback;
 }
 
-namespace {
+void GroupStage::pack(char* in) const { pack_parts(in, at_.in, src_, at_.n_in); }
 
-size_t up8(size_t b) { return (b + 7) & ~size_t(7); }
+sr_status GroupStage::check(const char* who, const Workload& w, const std::vector<int64_t>& node_free, bool more_ok,
+                            std::string* err) {
+  at_ = GroupLayout{};
+  w_ = &w;
+  return stage_workload(who, w, node_free, more_ok, &prog_, at_.in, src_, err);
+}
 
-}  // namespace
-
-sr_status BlockersStage::plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap,
-                              const sr_cluster* c, const sr_candidates* cands, BlockerWays* ways, bool want_counts,
-                              std::string* err) {
-  const size_t na = w.pod_src.size(), n_pad = static_cast<size_t>(w.n_pad);
-  if (!build_explain(w, &prog_) || w.pod_cls.size() != na || w.n_pad != w.Wp * 64 || node_free.size() < 3 * n_pad) {
-    *err = "blockers: the encoder left no reasons";
-    return SR_ERR_STATE;
-  }
-  for (int32_t op : prog_.ops)  // what the kernel indexes with
-    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > X_ALL) {
-      *err = "blockers: malformed program";
-      return SR_ERR_STATE;
-    }
+sr_status GroupStage::plan_groups(const std::string& who, const char* what_pods, const sr_cluster* c,
+                                  const sr_candidates* groups, const std::vector<int32_t>& ids, size_t pod_cap,
+                                  std::vector<int32_t>* dropped, std::string* err) {
+  const Workload& w = *w_;
+  const size_t na = w.pod_src.size();
   std::vector<ExplainPod> xp;
   explain_pods(w, &xp);
-  const int32_t* off = cands->cand_pod_off;
+  const int32_t* off = groups->cand_pod_off;
   size_t flat = 0;
-  for (int32_t b : ways->batched) flat += static_cast<size_t>(off[b + 1] - off[b]);
+  for (int32_t g : ids) flat += static_cast<size_t>(off[g + 1] - off[g]);
   if (w.status_host.size() != flat) {
-    *err = "blockers: the encode is not of the batched candidates' pods";
+    *err = who + ": the encode is not of " + what_pods;
     return SR_ERR_STATE;
   }
   std::vector<int32_t> active(flat, -1);  // flat pod -> active pod
   for (size_t q = 0; q < na; ++q) {
     const int32_t i = w.pod_src[q] - w.pod_base;
     if (i < 0 || static_cast<size_t>(i) >= flat || xp[q].cls < 0 || xp[q].cls >= w.n_classes) {
-      *err = "blockers: pod source or class out of range";
+      *err = who + ": pod source or class out of range";
       return SR_ERR_STATE;
     }
     active[i] = static_cast<int32_t>(q);
   }
   pods_.clear();
   kept_.clear();
-  coff_.assign(1, 0);
+  goff_.assign(1, 0);
   size_t f0 = 0;
-  for (int32_t b : ways->batched) {
-    const size_t np = static_cast<size_t>(off[b + 1] - off[b]);
-    bool keep = np <= static_cast<size_t>(kBlockersCtx);
+  for (int32_t g : ids) {
+    const size_t np = static_cast<size_t>(off[g + 1] - off[g]);
+    bool keep = np <= pod_cap;
     for (size_t k = 0; k < np; ++k) keep = keep && active[f0 + k] >= 0 && w.status_host[f0 + k] != SR_CAND_FALLBACK;
     if (keep) {
       for (size_t k = 0; k < np; ++k) {
         BlockerPod bp;
         bp.p = xp[active[f0 + k]];
-        for (int d = 0; d < 3; ++d) bp.acc[d] = pod_acc(c, cands->cand_pods[off[b] + k], d);
+        for (int d = 0; d < 3; ++d) bp.acc[d] = pod_acc(c, groups->cand_pods[off[g] + k], d);
         pods_.push_back(bp);
       }
-      kept_.push_back(b);
-      coff_.push_back(static_cast<int32_t>(pods_.size()));
+      kept_.push_back(g);
+      goff_.push_back(static_cast<int32_t>(pods_.size()));
     } else {
-      ways->how[b] = SR_EXPLAIN_SINGLE;
+      dropped->push_back(g);
     }
     f0 += np;
   }
-  node_left(snap, w.n_pad, &left_);
-  w_ = &w;
-  free_ = node_free.data();
-  counts_ = want_counts;
-  const size_t np = pods_.size(), nk = kept_.size();
-  at_ = BlockersLayout{};
-  at_.atoms = 0;
-  at_.free = up8(at_.atoms + w.atoms.size() * 8);
-  at_.xoff = up8(at_.free + 3 * n_pad * 8);
-  at_.xops = up8(at_.xoff + prog_.off.size() * 4);
-  at_.pods = up8(at_.xops + prog_.ops.size() * 4);
-  at_.coff = up8(at_.pods + np * sizeof(BlockerPod));
-  at_.left = up8(at_.coff + coff_.size() * 4);
-  at_.in_bytes = up8(at_.left + left_.size() * 8);
-  at_.counts = 0;
-  at_.zero_bytes = counts_ ? np * SR_WHY_COUNT * 4 : 0;
-  at_.node_of_pod = up8(at_.zero_bytes);
-  at_.blockers = up8(at_.node_of_pod + np * 4);
-  at_.first = up8(at_.blockers + nk * 4);
-  at_.out_bytes = up8(at_.first + nk * 4);
+  part_of(&at_.in[IN_PODS], &src_[IN_PODS], pods_.data(), pods_.size());
+  part_of(&at_.in[GIN_OFF], &src_[GIN_OFF], goff_.data(), goff_.size());
   return SR_OK;
 }
 
-void BlockersStage::pack(char* in) const {
-  auto put = [&](size_t at, const void* src, size_t bytes) {
-    if (bytes) std::memcpy(in + at, src, bytes);
-  };
-  put(at_.atoms, w_->atoms.data(), w_->atoms.size() * 8);
-  put(at_.free, free_, 3 * static_cast<size_t>(w_->n_pad) * 8);
-  put(at_.xoff, prog_.off.data(), prog_.off.size() * 4);
-  put(at_.xops, prog_.ops.data(), prog_.ops.size() * 4);
-  put(at_.pods, pods_.data(), pods_.size() * sizeof(BlockerPod));
-  put(at_.coff, coff_.data(), coff_.size() * 4);
-  put(at_.left, left_.data(), left_.size() * 8);
+void GroupStage::lay_out(const sr_snapshot* snap, int n_in, bool want_counts) {
+  node_left(snap, w_->n_pad, &left_);
+  counts_ = want_counts;
+  at_.n_in = n_in;
+  part_of(&at_.in[n_in - 1], &src_[n_in - 1], left_.data(), left_.size());
+  at_.in_bytes = up8(place(at_.in, n_in));
+  const size_t np = pods_.size(), nk = kept_.size();
+  part_of<int32_t>(&at_.out[GOUT_COUNTS], nullptr, nullptr, counts_ ? np * SR_WHY_COUNT : 0);
+  part_of<int32_t>(&at_.out[GOUT_NODE_OF_POD], nullptr, nullptr, np);
+  part_of<int32_t>(&at_.out[GOUT_COUNT], nullptr, nullptr, nk);
+  part_of<int32_t>(&at_.out[GOUT_FIRST], nullptr, nullptr, nk);
+  at_.out_bytes = up8(place(at_.out, GOUT_PARTS));
+  at_.zero_bytes = at_.out[GOUT_COUNTS].bytes;
+}
+
+void GroupStage::in_args(const char* in, ExplainArgs* x, const BlockerPod** pods, const int32_t** off,
+                         const int64_t** left) const {
+  stage_args(*w_, n_pods(), in, at_.in, x);
+  *pods = at_part<BlockerPod>(in, at_.in[IN_PODS]);
+  *off = at_part<int32_t>(in, at_.in[GIN_OFF]);
+  *left = at_part<int64_t>(in, at_.in[at_.n_in - 1]);
+}
+
+void GroupStage::out_args(char* out, int32_t** counts, int32_t** node_of_pod, int32_t** count, int32_t** first) const {
+  *counts = counts_ ? at_part<int32_t>(out, at_.out[GOUT_COUNTS]) : nullptr;
+  *node_of_pod = at_part<int32_t>(out, at_.out[GOUT_NODE_OF_POD]);
+  *count = at_part<int32_t>(out, at_.out[GOUT_COUNT]);
+  *first = at_part<int32_t>(out, at_.out[GOUT_FIRST]);
+}
+
+void GroupStage::unpack_groups(const char* image, const sr_candidates* groups, const GroupResults& r) const {
+  const int32_t* counts = at_part<int32_t>(image, at_.out[GOUT_COUNTS]);
+  const int32_t* map = at_part<int32_t>(image, at_.out[GOUT_NODE_OF_POD]);
+  const int32_t* count = at_part<int32_t>(image, at_.out[GOUT_COUNT]);
+  const int32_t* first = at_part<int32_t>(image, at_.out[GOUT_FIRST]);
+  const int32_t* off = groups->cand_pod_off;
+  for (size_t j = 0; j < kept_.size(); ++j) {
+    const int32_t g = kept_[j];
+    const size_t p0 = static_cast<size_t>(off[g] - off[0]), k0 = static_cast<size_t>(goff_[j]);
+    const size_t np = static_cast<size_t>(goff_[j + 1] - goff_[j]);
+    r.count[g] = count[j];
+    r.first[g] = first[j];
+    if (np) std::copy_n(map + k0, np, r.node_of_pod + p0);
+    if (counts_ && r.counts && np) std::copy_n(counts + k0 * SR_WHY_COUNT, np * SR_WHY_COUNT, r.counts + p0 * SR_WHY_COUNT);
+    if (r.mark) r.mark[g] = r.marked;
+  }
+}
+
+sr_status BlockersStage::plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap,
+                              const sr_cluster* c, const sr_candidates* cands, BlockerWays* ways, bool want_counts,
+                              std::string* err) {
+  sr_status st = check("blockers", w, node_free, true, err);
+  if (st != SR_OK) return st;
+  std::vector<int32_t> left;  // the candidates that leave the batch
+  st = plan_groups("blockers", "the batched candidates' pods", c, cands, ways->batched, kBlockersCtx, &left, err);
+  if (st != SR_OK) return st;
+  for (int32_t b : left) ways->how[b] = SR_EXPLAIN_SINGLE;
+  lay_out(snap, BIN_PARTS, want_counts);
+  return SR_OK;
 }
 
 void BlockersStage::args(const char* in, char* out, BlockersArgs* a) const {
   *a = BlockersArgs{};
-  a->x.n_spot = w_->n_spot;
-  a->x.n_pad = w_->n_pad;
-  a->x.Wp = w_->Wp;
-  a->x.n_pods = n_pods();
-  a->x.atoms = reinterpret_cast<const uint64_t*>(in + at_.atoms);
-  a->x.node_free = reinterpret_cast<const int64_t*>(in + at_.free);
-  a->x.xoff = reinterpret_cast<const int32_t*>(in + at_.xoff);
-  a->x.xops = reinterpret_cast<const int32_t*>(in + at_.xops);
-  a->pods = reinterpret_cast<const BlockerPod*>(in + at_.pods);
-  a->cand_off = reinterpret_cast<const int32_t*>(in + at_.coff);
-  a->node_left = reinterpret_cast<const int64_t*>(in + at_.left);
+  in_args(in, &a->x, &a->pods, &a->cand_off, &a->node_left);
   a->n_cand = n_cand();
-  a->counts = counts_ ? reinterpret_cast<int32_t*>(out + at_.counts) : nullptr;
-  a->node_of_pod = reinterpret_cast<int32_t*>(out + at_.node_of_pod);
-  a->blockers = reinterpret_cast<int32_t*>(out + at_.blockers);
-  a->first = reinterpret_cast<int32_t*>(out + at_.first);
+  out_args(out, &a->counts, &a->node_of_pod, &a->blockers, &a->first);
 }
 
 void BlockersStage::unpack(const char* image, const sr_candidates* cands, sr_blockers_out* out) const {
-  const int32_t* counts = reinterpret_cast<const int32_t*>(image + at_.counts);
-  const int32_t* map = reinterpret_cast<const int32_t*>(image + at_.node_of_pod);
-  const int32_t* blockers = reinterpret_cast<const int32_t*>(image + at_.blockers);
-  const int32_t* first = reinterpret_cast<const int32_t*>(image + at_.first);
-  const int32_t* off = cands->cand_pod_off;
-  for (size_t j = 0; j < kept_.size(); ++j) {
-    const int32_t c = kept_[j];
-    const size_t p0 = static_cast<size_t>(off[c] - off[0]), k0 = static_cast<size_t>(coff_[j]);
-    const size_t np = static_cast<size_t>(coff_[j + 1] - coff_[j]);
-    out->blockers[c] = blockers[j];
-    out->first[c] = first[j];
-    std::copy_n(map + k0, np, out->node_of_pod + p0);
-    if (counts_ && out->counts) std::copy_n(counts + k0 * SR_WHY_COUNT, np * SR_WHY_COUNT, out->counts + p0 * SR_WHY_COUNT);
-    if (out->fallback) out->fallback[c] = 0;
-  }
+  unpack_groups(image, cands, GroupResults{out->blockers, out->first, out->node_of_pod, out->counts, out->fallback, 0});
 }
 
 }  // namespace sr

@@ -7,7 +7,9 @@
 // Fork: its own placements are a list of {node, pods, acc[3]} sorted by node (PlanCtxEntry) that grows as the
 // loop goes, and every pod is judged by explain_node_ctx against the snapshot as it is plus that list.
 // blockers_candidate is that loop on the host, the statement the kernel of blockers.hip follows, one
-// candidate per wave.  BlockersStage lays out, packs and unpacks the two buffers of the batched pass.
+// candidate per wave.  BlockersStage lays out, packs and unpacks the two buffers of the batched pass, which
+// query.cpp owns; what it shares with sr_evacuate_plan's stage -- groups of pods (candidates here, scenarios
+// there) planned one after the other by one kernel -- is GroupStage.
 #pragma once
 
 #include <cstddef>
@@ -15,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "explain_args.hpp"
+#include "stage_base.hpp"
 
 struct sr_snapshot;
 
@@ -76,20 +78,77 @@ struct BlockersArgs {
   int32_t* first;            // [n_cand]
 };
 
-struct BlockersLayout {
-  // input buffer: atoms, node_free [3][n_pad], xoff, xops, pods, cand_off, node_left; each at the 8-byte
-  // boundary after the one before
-  size_t atoms = 0, free = 0, xoff = 0, xops = 0, pods = 0, coff = 0, left = 0, in_bytes = 0;
-  // output buffer: counts (absent when not wanted: the zeroed prefix), node_of_pod, blockers, first
-  size_t counts = 0, node_of_pod = 0, blockers = 0, first = 0, zero_bytes = 0, out_bytes = 0;
+// The two buffers of a pass over groups of pods, as part tables (stage_base.hpp).  Input: the common parts
+// (IN_PODS: BlockerPod), GIN_OFF, the unit's own parts, and the nodes' pod slack last.  Output: GOUT_*.
+constexpr int GIN_OFF = IN_COMMON;  // int32 [groups + 1] into the pods
+constexpr int kGroupInMax = IN_COMMON + 4;
+enum GroupOut {
+  GOUT_COUNTS,       // int32 [n_pods][SR_WHY_COUNT]; absent when not wanted; the zeroed prefix
+  GOUT_NODE_OF_POD,  // int32 [n_pods]
+  GOUT_COUNT,        // int32 [groups]: blockers / stranded
+  GOUT_FIRST,        // int32 [groups]
+  GOUT_PARTS
+};
+struct GroupLayout {
+  StagePart in[kGroupInMax], out[GOUT_PARTS];
+  int n_in = 0;  // parts of `in` in use
+  size_t in_bytes = 0, zero_bytes = 0, out_bytes = 0;
+};
+// sr_blockers_plan's input: the common parts, cand_off, node_left
+enum BlockersIn { BIN_COFF = GIN_OFF, BIN_LEFT, BIN_PARTS };
+using BlockersLayout = GroupLayout;
+
+// The caller's arrays a pass over groups fills, by the caller's group and pod indices.
+struct GroupResults {
+  int32_t *count, *first, *node_of_pod, *counts;
+  uint8_t* mark;  // [groups] or nullptr: set to `marked` for every group the kernel planned
+  uint8_t marked;
+};
+
+// What BlockersStage and EvacuateStage share.  Valid while the workload, node_free and the groups given to
+// plan_groups() stand.
+class GroupStage {
+ public:
+  const GroupLayout& at() const { return at_; }
+  int32_t n_pods() const { return static_cast<int32_t>(pods_.size()); }
+  const ExplainPrograms& programs() const { return prog_; }
+  void pack(char* in) const;  // at().in_bytes
+
+ protected:
+  // plan() in three steps.  check(): stage_workload over `w`, the errors starting with `who`.
+  sr_status check(const char* who, const Workload& w, const std::vector<int64_t>& node_free, bool more_ok, std::string* err);
+  // plan_groups(): check()'s `w` is the encode (tags on) of the pods of the groups `ids` of `groups`, flattened in that
+  // order, as single-pod candidates (`what_pods` names them in an error).  Keeps every group of at most
+  // `pod_cap` pods none of whose pods the encode handed back as fallback or left inactive: its BlockerPods, its
+  // id in kept_, its end in goff_.  The others are appended to *dropped.
+  sr_status plan_groups(const std::string& who, const char* what_pods, const sr_cluster* c, const sr_candidates* groups,
+                        const std::vector<int32_t>& ids, size_t pod_cap, std::vector<int32_t>* dropped, std::string* err);
+  // After plan_groups() and the unit's own parts in at_.in[GIN_OFF + 1 ..]: node_left as part n_in - 1, both
+  // buffers laid out.
+  void lay_out(const sr_snapshot* snap, int n_in, bool want_counts);
+  int32_t n_groups() const { return static_cast<int32_t>(kept_.size()); }
+  // The arguments every such kernel takes: the ExplainArgs prefix, the pods, the group offsets, node_left.
+  void in_args(const char* in, ExplainArgs* x, const BlockerPod** pods, const int32_t** off, const int64_t** left) const;
+  // ... and its four outputs (counts nullptr when not wanted)
+  void out_args(char* out, int32_t** counts, int32_t** node_of_pod, int32_t** count, int32_t** first) const;
+  // The first at().out_bytes of the output buffer into the caller's arrays.
+  void unpack_groups(const char* image, const sr_candidates* groups, const GroupResults& r) const;
+
+  ExplainPrograms prog_;
+  std::vector<BlockerPod> pods_;
+  std::vector<int32_t> goff_, kept_;  // the kernel's groups: their pods, the caller's indices
+  std::vector<int64_t> left_;
+  const Workload* w_ = nullptr;
+  const void* src_[kGroupInMax] = {};
+  GroupLayout at_;
+  bool counts_ = false;
 };
 
 // Every output of candidate c as "not judged": blockers / first -1, its pods -1, zero rows, fallback as given.
 void blockers_clear(const sr_candidates* cands, int32_t c, uint8_t fallback, sr_blockers_out* out);
 
-// The staging of the batched pass.  Valid while the workload, node_free and the candidates given to plan()
-// stand.
-class BlockersStage {
+// The staging of the batched pass.
+class BlockersStage : public GroupStage {
  public:
   // `w`: the encode (tags on) of blockers_flat's pods as single-pod candidates.  A candidate one of whose
   // pods that encode handed back as fallback (or left inactive) leaves the batch: ways->how[c] becomes
@@ -97,24 +156,10 @@ class BlockersStage {
   // holds something the kernel would index out of bounds with.
   sr_status plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap, const sr_cluster* c,
                  const sr_candidates* cands, BlockerWays* ways, bool want_counts, std::string* err);
-  const BlockersLayout& at() const { return at_; }
-  int32_t n_cand() const { return static_cast<int32_t>(kept_.size()); }  // candidates the kernel plans
-  int32_t n_pods() const { return static_cast<int32_t>(pods_.size()); }
-  const ExplainPrograms& programs() const { return prog_; }
-  void pack(char* in) const;  // at().in_bytes
+  int32_t n_cand() const { return n_groups(); }  // candidates the kernel plans
   void args(const char* in, char* out, BlockersArgs* a) const;
   // the first at().out_bytes of the output buffer into the caller's arrays
   void unpack(const char* image, const sr_candidates* cands, sr_blockers_out* out) const;
-
- private:
-  ExplainPrograms prog_;
-  std::vector<BlockerPod> pods_;
-  std::vector<int32_t> coff_, kept_;  // the kernel's candidates: their pods, their local positions
-  std::vector<int64_t> left_;
-  const Workload* w_ = nullptr;
-  const int64_t* free_ = nullptr;
-  BlockersLayout at_;
-  bool counts_ = false;
 };
 
 }  // namespace sr

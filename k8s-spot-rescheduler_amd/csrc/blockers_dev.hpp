@@ -1,4 +1,4 @@
-// blockers_dev.hpp — the launch of sr_blockers_plan's kernel (blockers.hip), for planner.cpp.
+// blockers_dev.hpp — the launch of sr_blockers_plan's kernel (blockers.hip), for query.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -2,8 +2,8 @@
 #include "evacuate.hpp"
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
-#include <cstring>
 
 #include "host.hpp"
 
@@ -118,12 +118,6 @@ void evacuate_clear(const sr_candidates* scen, int32_t s, uint8_t how, sr_evacua
   if (out->how) out->how[s] = how;
 }
 
-namespace {
-
-size_t up8(size_t b) { return (b + 7) & ~size_t(7); }
-
-}  // namespace
-
 EvacuateScratch evacuate_scratch(int32_t n_pad, int32_t blocks) {
   EvacuateScratch s;
   const size_t cells = static_cast<size_t>(std::max(blocks, 0)) * static_cast<size_t>(std::max(n_pad, 0));
@@ -145,156 +139,51 @@ sr_status EvacuateStage::plan(const Workload& w, const std::vector<int64_t>& nod
                               const sr_cluster* c, const sr_candidates* scen, const int32_t* lost_off,
                               const int32_t* lost_pos, const std::vector<int32_t>& ids, bool want_counts,
                               std::vector<int32_t>* fell, std::string* err) {
-  const size_t na = w.pod_src.size(), n_pad = static_cast<size_t>(w.n_pad);
-  if (!build_explain(w, &prog_) || w.pod_cls.size() != na || w.n_pad != w.Wp * 64 || node_free.size() < 3 * n_pad ||
-      static_cast<size_t>(w.n_spot) != snap->nodes.size() || w.n_spot > w.n_pad) {
-    *err = "evacuate: the encoder left no reasons";
-    return SR_ERR_STATE;
-  }
+  const bool sizes_ok = static_cast<size_t>(w.n_spot) == snap->nodes.size() && w.n_spot <= w.n_pad;
+  sr_status st = check("evacuate", w, node_free, sizes_ok, err);
+  if (st != SR_OK) return st;
   if (w.Wp > kEvacMaxWp) {
     *err = "evacuate: more spot nodes than the lost set's bitmask holds";
     return SR_ERR_STATE;
   }
-  for (int32_t op : prog_.ops)  // what the kernel indexes with
-    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > X_ALL) {
-      *err = "evacuate: malformed program";
-      return SR_ERR_STATE;
-    }
-  std::vector<ExplainPod> xp;
-  explain_pods(w, &xp);
-  const int32_t* off = scen->cand_pod_off;
-  size_t flat = 0;
-  for (int32_t s : ids) flat += static_cast<size_t>(off[s + 1] - off[s]);
-  if (w.status_host.size() != flat) {
-    *err = "evacuate: the encode is not of the scenarios' pods";
-    return SR_ERR_STATE;
-  }
-  std::vector<int32_t> active(flat, -1);  // flat pod -> active pod
-  for (size_t q = 0; q < na; ++q) {
-    const int32_t i = w.pod_src[q] - w.pod_base;
-    if (i < 0 || static_cast<size_t>(i) >= flat || xp[q].cls < 0 || xp[q].cls >= w.n_classes) {
-      *err = "evacuate: pod source or class out of range";
-      return SR_ERR_STATE;
-    }
-    active[i] = static_cast<int32_t>(q);
-  }
-  pods_.clear();
-  kept_.clear();
+  st = plan_groups("evacuate", "the scenarios' pods", c, scen, ids, SIZE_MAX, fell, err);
+  if (st != SR_OK) return st;
   lpos_.clear();
-  soff_.assign(1, 0);
   loff_.assign(1, 0);
-  size_t f0 = 0;
-  for (int32_t s : ids) {
-    const size_t np = static_cast<size_t>(off[s + 1] - off[s]);
-    bool keep = true;
-    for (size_t k = 0; k < np; ++k) keep = keep && active[f0 + k] >= 0 && w.status_host[f0 + k] != SR_CAND_FALLBACK;
-    if (keep) {
-      for (size_t k = 0; k < np; ++k) {
-        BlockerPod bp;
-        bp.p = xp[active[f0 + k]];
-        for (int d = 0; d < 3; ++d) bp.acc[d] = pod_acc(c, scen->cand_pods[off[s] + k], d);
-        pods_.push_back(bp);
+  for (int32_t s : kept_) {
+    for (int32_t j = lost_off[s]; j < lost_off[s + 1]; ++j) {
+      if (lost_pos[j] < 0 || lost_pos[j] >= w.n_spot) {  // (evacuate_ways checked it: the kernel sets an LDS bit with it)
+        *err = "evacuate: lost position out of range";
+        return SR_ERR_STATE;
       }
-      kept_.push_back(s);
-      soff_.push_back(static_cast<int32_t>(pods_.size()));
-      for (int32_t j = lost_off[s]; j < lost_off[s + 1]; ++j) {
-        if (lost_pos[j] < 0 || lost_pos[j] >= w.n_spot) {  // (evacuate_ways checked it: the kernel sets an LDS bit with it)
-          *err = "evacuate: lost position out of range";
-          return SR_ERR_STATE;
-        }
-        lpos_.push_back(lost_pos[j]);
-      }
-      loff_.push_back(static_cast<int32_t>(lpos_.size()));
-    } else {
-      fell->push_back(s);
+      lpos_.push_back(lost_pos[j]);
     }
-    f0 += np;
+    loff_.push_back(static_cast<int32_t>(lpos_.size()));
   }
-  node_left(snap, w.n_pad, &left_);
-  w_ = &w;
-  free_ = node_free.data();
-  counts_ = want_counts;
-  const size_t np = pods_.size(), nk = kept_.size();
-  at_ = EvacuateLayout{};
-  at_.atoms = 0;
-  at_.free = up8(at_.atoms + w.atoms.size() * 8);
-  at_.xoff = up8(at_.free + 3 * n_pad * 8);
-  at_.xops = up8(at_.xoff + prog_.off.size() * 4);
-  at_.pods = up8(at_.xops + prog_.ops.size() * 4);
-  at_.soff = up8(at_.pods + np * sizeof(BlockerPod));
-  at_.loff = up8(at_.soff + soff_.size() * 4);
-  at_.lpos = up8(at_.loff + loff_.size() * 4);
-  at_.left = up8(at_.lpos + lpos_.size() * 4);
-  at_.in_bytes = up8(at_.left + left_.size() * 8);
-  at_.counts = 0;
-  at_.zero_bytes = counts_ ? np * SR_WHY_COUNT * 4 : 0;
-  at_.node_of_pod = up8(at_.zero_bytes);
-  at_.stranded = up8(at_.node_of_pod + np * 4);
-  at_.first = up8(at_.stranded + nk * 4);
-  at_.out_bytes = up8(at_.first + nk * 4);
+  part_of(&at_.in[EIN_LOFF], &src_[EIN_LOFF], loff_.data(), loff_.size());
+  part_of(&at_.in[EIN_LPOS], &src_[EIN_LPOS], lpos_.data(), lpos_.size());
+  lay_out(snap, EIN_PARTS, want_counts);
   return SR_OK;
 }
 
 int32_t EvacuateStage::n_pad() const { return w_ ? w_->n_pad : 0; }
 
-void EvacuateStage::pack(char* in) const {
-  auto put = [&](size_t at, const void* src, size_t bytes) {
-    if (bytes) std::memcpy(in + at, src, bytes);
-  };
-  put(at_.atoms, w_->atoms.data(), w_->atoms.size() * 8);
-  put(at_.free, free_, 3 * static_cast<size_t>(w_->n_pad) * 8);
-  put(at_.xoff, prog_.off.data(), prog_.off.size() * 4);
-  put(at_.xops, prog_.ops.data(), prog_.ops.size() * 4);
-  put(at_.pods, pods_.data(), pods_.size() * sizeof(BlockerPod));
-  put(at_.soff, soff_.data(), soff_.size() * 4);
-  put(at_.loff, loff_.data(), loff_.size() * 4);
-  put(at_.lpos, lpos_.data(), lpos_.size() * 4);
-  put(at_.left, left_.data(), left_.size() * 8);
-}
-
 void EvacuateStage::args(const char* in, char* out, char* scratch, int32_t blocks, int32_t waves, EvacuateArgs* a) const {
   *a = EvacuateArgs{};
-  a->x.n_spot = w_->n_spot;
-  a->x.n_pad = w_->n_pad;
-  a->x.Wp = w_->Wp;
-  a->x.n_pods = n_pods();
-  a->x.atoms = reinterpret_cast<const uint64_t*>(in + at_.atoms);
-  a->x.node_free = reinterpret_cast<const int64_t*>(in + at_.free);
-  a->x.xoff = reinterpret_cast<const int32_t*>(in + at_.xoff);
-  a->x.xops = reinterpret_cast<const int32_t*>(in + at_.xops);
-  a->pods = reinterpret_cast<const BlockerPod*>(in + at_.pods);
-  a->scen_off = reinterpret_cast<const int32_t*>(in + at_.soff);
-  a->lost_off = reinterpret_cast<const int32_t*>(in + at_.loff);
-  a->lost_pos = reinterpret_cast<const int32_t*>(in + at_.lpos);
-  a->node_left = reinterpret_cast<const int64_t*>(in + at_.left);
+  in_args(in, &a->x, &a->pods, &a->scen_off, &a->node_left);
+  a->lost_off = at_part<int32_t>(in, at_.in[EIN_LOFF]);
+  a->lost_pos = at_part<int32_t>(in, at_.in[EIN_LPOS]);
   a->n_scen = n_scen();
   a->waves = waves;
   const EvacuateScratch sc = evacuate_scratch(w_->n_pad, blocks);
   a->used = reinterpret_cast<int64_t*>(scratch + sc.used);
   a->added = reinterpret_cast<int32_t*>(scratch + sc.added);
-  a->counts = counts_ ? reinterpret_cast<int32_t*>(out + at_.counts) : nullptr;
-  a->node_of_pod = reinterpret_cast<int32_t*>(out + at_.node_of_pod);
-  a->stranded = reinterpret_cast<int32_t*>(out + at_.stranded);
-  a->first = reinterpret_cast<int32_t*>(out + at_.first);
+  out_args(out, &a->counts, &a->node_of_pod, &a->stranded, &a->first);
 }
 
 void EvacuateStage::unpack(const char* image, const sr_candidates* scen, sr_evacuate_out* out) const {
-  const int32_t* counts = reinterpret_cast<const int32_t*>(image + at_.counts);
-  const int32_t* map = reinterpret_cast<const int32_t*>(image + at_.node_of_pod);
-  const int32_t* stranded = reinterpret_cast<const int32_t*>(image + at_.stranded);
-  const int32_t* first = reinterpret_cast<const int32_t*>(image + at_.first);
-  const int32_t* off = scen->cand_pod_off;
-  for (size_t j = 0; j < kept_.size(); ++j) {
-    const int32_t s = kept_[j];
-    const size_t p0 = static_cast<size_t>(off[s] - off[0]), k0 = static_cast<size_t>(soff_[j]);
-    const size_t np = static_cast<size_t>(soff_[j + 1] - soff_[j]);
-    out->stranded[s] = stranded[j];
-    out->first[s] = first[j];
-    if (np) std::copy_n(map + k0, np, out->node_of_pod + p0);
-    if (counts_ && out->counts && np)
-      std::copy_n(counts + k0 * SR_WHY_COUNT, np * SR_WHY_COUNT, out->counts + p0 * SR_WHY_COUNT);
-    if (out->how) out->how[s] = SR_EVAC_JUDGED;
-  }
+  unpack_groups(image, scen,
+                GroupResults{out->stranded, out->first, out->node_of_pod, out->counts, out->how, SR_EVAC_JUDGED});
 }
 
 }  // namespace sr

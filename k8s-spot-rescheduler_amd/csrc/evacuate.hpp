@@ -9,7 +9,7 @@
 // placements are dense per-node deltas (used[3][n_pad], added[n_pad]) that the scenario restores to zero by
 // walking its own node_of_pod, so the pod count has no limit.  evacuate_scenario is that loop on the host, the
 // statement the kernel of evacuate.hip follows, a block of waves a scenario.  EvacuateStage lays out, packs
-// and unpacks the two buffers of a pass.
+// and unpacks the two buffers of a pass, which query.cpp owns (GroupStage of blockers.hpp with the lost lists).
 #pragma once
 
 #include <cstddef>
@@ -81,13 +81,9 @@ struct EvacuateArgs {
   int32_t* first;            // [n_scen]
 };
 
-struct EvacuateLayout {
-  // input buffer: atoms, node_free [3][n_pad], xoff, xops, pods, scen_off, lost_off, lost_pos, node_left; each at
-  // the 8-byte boundary after the one before
-  size_t atoms = 0, free = 0, xoff = 0, xops = 0, pods = 0, soff = 0, loff = 0, lpos = 0, left = 0, in_bytes = 0;
-  // output buffer: counts (absent when not wanted: the zeroed prefix), node_of_pod, stranded, first
-  size_t counts = 0, node_of_pod = 0, stranded = 0, first = 0, zero_bytes = 0, out_bytes = 0;
-};
+// A pass's input: the common parts, scen_off, lost_off, lost_pos, node_left
+enum EvacuateIn { EIN_SOFF = GIN_OFF, EIN_LOFF, EIN_LPOS, EIN_LEFT, EIN_PARTS };
+using EvacuateLayout = GroupLayout;
 
 // The scratch of a launch of `blocks` blocks: used at 0, added behind it.
 struct EvacuateScratch {
@@ -103,7 +99,7 @@ void evacuate_shape(int32_t n_scen, const char* grid_env, const char* waves_env,
 void evacuate_clear(const sr_candidates* scen, int32_t s, uint8_t how, sr_evacuate_out* out);
 
 // The staging of one pass.  Valid while the workload, node_free and the arguments given to plan() stand.
-class EvacuateStage {
+class EvacuateStage : public GroupStage {
  public:
   // `w`: the encode (tags on) of evacuate_flat(ids)'s pods as single-pod candidates.  A scenario one of whose
   // pods that encode handed back as fallback (or left inactive) is not planned: it is appended to *fell.
@@ -111,26 +107,15 @@ class EvacuateStage {
   sr_status plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap, const sr_cluster* c,
                  const sr_candidates* scen, const int32_t* lost_off, const int32_t* lost_pos,
                  const std::vector<int32_t>& ids, bool want_counts, std::vector<int32_t>* fell, std::string* err);
-  const EvacuateLayout& at() const { return at_; }
-  int32_t n_scen() const { return static_cast<int32_t>(kept_.size()); }  // scenarios the kernel plans
-  int32_t n_pods() const { return static_cast<int32_t>(pods_.size()); }
+  int32_t n_scen() const { return n_groups(); }  // scenarios the kernel plans
   int32_t n_pad() const;
-  const ExplainPrograms& programs() const { return prog_; }
-  void pack(char* in) const;  // at().in_bytes
   // `scratch`: evacuate_scratch(n_pad(), blocks) bytes, zero
   void args(const char* in, char* out, char* scratch, int32_t blocks, int32_t waves, EvacuateArgs* a) const;
   // the first at().out_bytes of the output buffer into the caller's arrays; how[s] becomes SR_EVAC_JUDGED
   void unpack(const char* image, const sr_candidates* scen, sr_evacuate_out* out) const;
 
  private:
-  ExplainPrograms prog_;
-  std::vector<BlockerPod> pods_;
-  std::vector<int32_t> soff_, kept_, loff_, lpos_;
-  std::vector<int64_t> left_;
-  const Workload* w_ = nullptr;
-  const int64_t* free_ = nullptr;
-  EvacuateLayout at_;
-  bool counts_ = false;
+  std::vector<int32_t> loff_, lpos_;  // the kept scenarios' lost lists
 };
 
 }  // namespace sr

@@ -1,4 +1,4 @@
-// evacuate_dev.hpp — the launch of sr_evacuate_plan's kernel (evacuate.hip), for planner.cpp.
+// evacuate_dev.hpp — the launch of sr_evacuate_plan's kernel (evacuate.hip), for query.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // explain_dev.hpp — launches of the explain and shortfall kernels (explain.hip, explain_plan.hip), shared with
-// planner.cpp.  Their arguments are explain_args.hpp's.
+// query.cpp.  Their arguments are explain_args.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -33,37 +33,41 @@ void clear_slot(sr_explain_out* out, sr_shortfall_out* sh, size_t o, size_t ns, 
   if (sh->node_short) std::fill_n(sh->node_short + o * ns * SR_SHORT_COUNT, ns * SR_SHORT_COUNT, int64_t(0));
 }
 
-namespace {
+void pack_parts(char* in, const StagePart* parts, const void* const* src, int n) {
+  for (int i = 0; i < n; ++i)
+    if (parts[i].bytes) std::memcpy(in + parts[i].off, src[i], parts[i].bytes);
+}
 
-size_t up8(size_t b) { return (b + 7) & ~size_t(7); }
-
-// Offsets from the sizes: every part at the 8-byte boundary after the one before.  Returns the last part's end.
-size_t place(StagePart* parts, int n) {
-  size_t end = 0;
-  for (int i = 0; i < n; ++i) {
-    parts[i].off = up8(end);
-    end = parts[i].off + parts[i].bytes;
+sr_status stage_workload(const char* who, const Workload& w, const std::vector<int64_t>& node_free, bool more_ok,
+                         ExplainPrograms* prog, StagePart* in, const void** src, std::string* err) {
+  const size_t n_pad = static_cast<size_t>(w.n_pad);
+  if (!build_explain(w, prog) || w.pod_cls.size() != w.pod_src.size() || w.n_pad != w.Wp * 64 ||
+      node_free.size() < 3 * n_pad || !more_ok) {
+    *err = std::string(who) + ": the encoder left no reasons";
+    return SR_ERR_STATE;
   }
-  return end;
+  for (int32_t op : prog->ops)  // what the kernel indexes with
+    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > X_ALL) {
+      *err = std::string(who) + ": malformed program";
+      return SR_ERR_STATE;
+    }
+  part_of(&in[IN_ATOMS], &src[IN_ATOMS], w.atoms.data(), w.atoms.size());
+  part_of(&in[IN_FREE], &src[IN_FREE], node_free.data(), 3 * n_pad);
+  part_of(&in[IN_XOFF], &src[IN_XOFF], prog->off.data(), prog->off.size());
+  part_of(&in[IN_XOPS], &src[IN_XOPS], prog->ops.data(), prog->ops.size());
+  return SR_OK;
 }
 
-template <class T>
-void part_of(StagePart* p, const void** src, const T* data, size_t count) {
-  p->bytes = count * sizeof(T);
-  p->elem = sizeof(T) > 8 ? 8 : sizeof(T);  // (the records are 8-byte aligned structs)
-  if (src) *src = data;
+void stage_args(const Workload& w, int32_t n_pods, const char* in, const StagePart* parts, ExplainArgs* a) {
+  a->n_spot = w.n_spot;
+  a->n_pad = w.n_pad;
+  a->Wp = w.Wp;
+  a->n_pods = n_pods;
+  a->atoms = at_part<uint64_t>(in, parts[IN_ATOMS]);
+  a->node_free = at_part<int64_t>(in, parts[IN_FREE]);
+  a->xoff = at_part<int32_t>(in, parts[IN_XOFF]);
+  a->xops = at_part<int32_t>(in, parts[IN_XOPS]);
 }
-
-template <class T>
-T* at_part(char* base, const StagePart& p) {
-  return reinterpret_cast<T*>(base + p.off);
-}
-template <class T>
-const T* at_part(const char* base, const StagePart& p) {
-  return reinterpret_cast<const T*>(base + p.off);
-}
-
-}  // namespace
 
 sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node_free, const sr_snapshot* snap,
                              const PlanQueries* pq, bool want_shortfall, bool node_mask, bool node_short,
@@ -73,19 +77,13 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
     node_mask = node_short = false;
   }
   const size_t na = w.pod_src.size(), ns = static_cast<size_t>(w.n_spot), n_pad = static_cast<size_t>(w.n_pad);
-  if (!build_explain(w, &prog_) || w.pod_cls.size() != na || w.n_pad != w.Wp * 64 || node_free.size() < 3 * n_pad) {
-    *err = "explain: the encoder left no reasons";
-    return SR_ERR_STATE;
-  }
+  at_ = StageLayout{};
+  const sr_status st = stage_workload("explain", w, node_free, true, &prog_, at_.in, src_, err);
+  if (st != SR_OK) return st;
   explain_pods(w, &pods_);
   for (const ExplainPod& p : pods_)
     if (p.cls < 0 || p.cls >= w.n_classes) {
       *err = "explain: pod class out of range";
-      return SR_ERR_STATE;
-    }
-  for (int32_t op : prog_.ops)  // what the kernel indexes with
-    if ((op >> 8) < 0 || (op >> 8) >= w.n_atoms || (op >> 3 & 31) >= SR_WHY_COUNT || (op & 7) > X_ALL) {
-      *err = "explain: malformed program";
       return SR_ERR_STATE;
     }
   if (pq) {
@@ -113,11 +111,6 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
     for (int32_t src : w.pod_src) slots_.push_back(view->slot ? view->slot[src - w.pod_base] : src - w.pod_base);
   }
 
-  at_ = StageLayout{};
-  part_of(&at_.in[IN_ATOMS], &src_[IN_ATOMS], w.atoms.data(), w.atoms.size());
-  part_of(&at_.in[IN_FREE], &src_[IN_FREE], node_free.data(), 3 * n_pad);
-  part_of(&at_.in[IN_XOFF], &src_[IN_XOFF], prog_.off.data(), prog_.off.size());
-  part_of(&at_.in[IN_XOPS], &src_[IN_XOPS], prog_.ops.data(), prog_.ops.size());
   part_of(&at_.in[IN_PODS], &src_[IN_PODS], pods_.data(), na);
   part_of(&at_.in[IN_CTX], &src_[IN_CTX], centries_.data(), lists_ ? centries_.size() : 0);
   part_of(&at_.in[IN_COFF], &src_[IN_COFF], coff_.data(), lists_ ? coff_.size() : 0);
@@ -153,8 +146,7 @@ sr_status ExplainStage::plan(const Workload& w, const std::vector<int64_t>& node
 }
 
 void ExplainStage::pack(char* in) const {
-  for (int i = 0; i < IN_PARTS; ++i)
-    if (at_.in[i].bytes) std::memcpy(in + at_.in[i].off, src_[i], at_.in[i].bytes);
+  pack_parts(in, at_.in, src_, IN_PARTS);
   if (at_.view_slot.bytes) std::memcpy(in + at_.view_slot.off, slots_.data(), at_.view_slot.bytes);
 }
 
@@ -162,14 +154,7 @@ void ExplainStage::args(const char* in, char* out, ExplainPlanArgs* pa, Shortfal
   *pa = ExplainPlanArgs{};
   *sa = ShortfallArgs{};
   ExplainArgs& a = pa->x;
-  a.n_spot = w_->n_spot;
-  a.n_pad = w_->n_pad;
-  a.Wp = w_->Wp;
-  a.n_pods = n_pods_;
-  a.atoms = at_part<uint64_t>(in, at_.in[IN_ATOMS]);
-  a.node_free = at_part<int64_t>(in, at_.in[IN_FREE]);
-  a.xoff = at_part<int32_t>(in, at_.in[IN_XOFF]);
-  a.xops = at_part<int32_t>(in, at_.in[IN_XOPS]);
+  stage_args(*w_, n_pods_, in, at_.in, &a);
   a.pods = at_part<ExplainPod>(in, at_.in[IN_PODS]);
   a.sums = at_part<int32_t>(out, at_.out[OUT_SUMS]);
   a.node_mask = want_mask_ ? at_part<uint16_t>(out, at_.out[OUT_MASKS]) : nullptr;

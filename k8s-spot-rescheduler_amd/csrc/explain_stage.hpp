@@ -2,17 +2,18 @@
 // sr_explain_plan, sr_shortfall_pods, sr_shortfall_plan): what goes up in one copy, what comes back in one,
 // and where each part lies.
 //
-// HIP-free.  planner.cpp's explain() owns the buffers, the stream and the launches; this unit validates
+// HIP-free.  query.cpp's explain() owns the buffers, the stream and the launches; this unit validates
 // what the kernels index with, lays the buffers out (plan), writes the input image (pack), points the kernel
-// arguments into the buffers (args) and reads the downloaded image into the caller's arrays (unpack).
+// arguments into the buffers (args) and reads the downloaded image into the caller's arrays (unpack).  The
+// part tables and the checks it shares with the blockers and evacuate stages are stage_base.hpp's.
 // tools/shortfall_check.cpp runs all four on the host over exact-size heap blocks, under the sanitizers.
 #pragma once
 
 #include <string>
 #include <vector>
 
-#include "explain_args.hpp"
 #include "node_view.hpp"
+#include "stage_base.hpp"
 
 struct sr_snapshot;
 
@@ -20,16 +21,10 @@ namespace sr {
 
 struct Workload;
 
-// The parts in buffer order.  A part starts at the 8-byte boundary after the part before it; an absent part
-// has no bytes.
+// The input parts in buffer order: stage_base.hpp's common ones (IN_PODS: ExplainPod), then
 enum StageIn {
-  IN_ATOMS,  // uint64 [n_atoms][Wp]
-  IN_FREE,   // int64 [3][n_pad]
-  IN_XOFF,   // int32 [n_classes + 1]
-  IN_XOPS,   // int32
-  IN_PODS,   // ExplainPod [n_pods]
-  IN_CTX,    // PlanCtxEntry, lists only
-  IN_COFF,   // int32 [n_pods + 1], lists only
+  IN_CTX = IN_COMMON,  // PlanCtxEntry, lists only
+  IN_COFF,             // int32 [n_pods + 1], lists only
   IN_SLACK,  // shortfall / node view: node_left, int64 [n_pad]; else with lists: node_slack, int32 [n_pad]; else absent
   IN_PARTS
 };
@@ -43,11 +38,6 @@ enum StageOut {
   OUT_PMIN,    // uint64 [n_pods][blocks][SR_SHORT_COUNT]: the blocks' partials stay on the device (shortfall only)
   OUT_PAT,     // int32 [n_pods][blocks][SR_SHORT_COUNT]
   OUT_PARTS
-};
-
-struct StagePart {
-  size_t off = 0, bytes = 0;
-  size_t elem = 8;  // size of the part's element type (what its offset must be a multiple of)
 };
 
 struct StageLayout {
@@ -72,7 +62,7 @@ void clear_slot(sr_explain_out* out, sr_shortfall_out* sh, size_t o, size_t n_sp
 // The node-view switch of plan(): the per-node reduction of sr_node_view_pods / sr_node_view_plan in place of
 // every per-query output.  The call's totals are no part of the two buffers: they live through the several
 // passes of one call (the batched pass and every SINGLE candidate), between which the output buffer may be
-// allocated anew, so planner.cpp keeps them in a buffer of their own, node_view_layout(node_view_stride(n_spot), 1)
+// allocated anew, so query.cpp keeps them in a buffer of their own, node_view_layout(node_view_stride(n_spot), 1)
 // long.  `judged` needs no device word: it is the number of active pods, which the host knows.
 struct NodeViewAsk {
   const int32_t* slot = nullptr;  // asked index -> slot, nullptr: the asked index (as unpack's `slot`)

@@ -1,4 +1,6 @@
-// planner.cpp — device context, resident buffers and the planning tick.
+// planner.cpp — device context, resident buffers and the planning tick.  (The read-only query calls --
+// sr_explain_*, sr_shortfall_*, sr_node_view_*, sr_blockers_plan, sr_evacuate_plan -- are query.cpp's; the
+// context holds their state as one member and shares the device, the stream and the error string with them.)
 //
 // sr_ctx plays the role of the reference's predicate checker (created once,
 // rescheduler.go:149).  One tick (sr_plan_run) is three kernels on a single
@@ -20,12 +22,10 @@
 #include <string>
 #include <vector>
 
-#include "blockers_dev.hpp"
-#include "evacuate_dev.hpp"
-#include "explain_dev.hpp"
-#include "explain_stage.hpp"
+#include "dev_buf.hpp"
 #include "host.hpp"
 #include "kernels.hpp"
+#include "query.hpp"
 #include "residency.hpp"
 #include "result_words.hpp"
 #include "seq_pdb.hpp"
@@ -67,15 +67,10 @@ const Rccl& rccl() {
   return r;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
+using sr::DevBuf;
+using sr::HostBuf;
+using sr::dev_reserve;
+using sr::host_reserve;
 
 // One workload slot: an encoded candidate input with its device arena and
 // pinned staging copy.  sr_plan_first's prefix batches and an every-candidate
@@ -207,66 +202,16 @@ struct sr_ctx {
   int32_t k2_map_regs = 1;    // SR_K2_MAP_REGS: the winner's mapping goes to the host from the wave's registers / LDS
   int32_t k2_node_kernel = 1; // SR_K2_NODE_KERNEL: node-order-only K2 kernel when every candidate takes that path
   int32_t s_head_only = 1;    // SR_S_HEAD_ONLY: K0 writes S-row heads only on rows wider than 64 words (0: never)
-  // sr_explain_pods: an encoder, a workload and buffers of its own, outside the slots, the workload arenas and
-  // the residency model, so a plan before and after an explain call encodes and uploads exactly the same
-  sr::EncoderCache x_enc;
-  sr::Workload x_wl;
-  sr::ExplainStage x_stage;  // what the call uploads, where each part of its two buffers lies (explain_stage.hpp)
-  DevBuf x_in, x_out;
-  HostBuf hx_in, hx_out;
-  // sr_node_view_*: the call's per-node totals, which every pass of one call accumulates into (x_out may be
-  // allocated anew between the passes)
-  DevBuf x_view;
-  HostBuf hx_view;
-  sr::BlockersStage b_stage;  // sr_blockers_plan: its batched pass through x_in / x_out (blockers.hpp)
-  // sr_evacuate_plan: its passes through x_in / x_out (evacuate.hpp), and the blocks' dense per-node deltas.
-  // The scratch is zero between launches -- every block restores its slice -- so it is zeroed on the stream
-  // only when it was allocated anew, or when a call ended before its launch was known to have finished
-  sr::EvacuateStage e_stage;
-  DevBuf e_scratch;
-  bool e_scratch_zero = false;
+  sr::QueryCtx query;  // the query calls' state (query.hpp): device, stream and &err are set by sr_create
 };
+
+sr::QueryCtx* sr::query_ctx(sr_ctx* ctx) { return &ctx->query; }
 
 namespace {
 
-sr_status hip_fail(sr_ctx* ctx, hipError_t e, const char* what) {
-  ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-  return SR_ERR_HIP;
-}
+std::string& err_string(sr_ctx* ctx) { return ctx->err; }  // (for HIP_TRY)
 
-#define HIP_TRY(ctx, expr)                                  \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return hip_fail((ctx), _e, #expr); \
-  } while (0)
-
-hipError_t dev_reserve(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  size_t cap = std::max<size_t>(bytes + bytes / 4, 4096);
-  hipError_t e = hipMalloc(&b.p, cap);
-  if (e == hipSuccess) b.cap = cap;
-  return e;
-}
-
-// Fresh pinned blocks are zeroed: the runtime may hand back memory an earlier
-// context freed, and the tagged result words (mapped memory) must never carry
-// a stale tag (run sequence numbers also come from one process-wide counter).
-hipError_t host_reserve(HostBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return hipSuccess;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  size_t cap = std::max<size_t>(bytes + bytes / 4, 4096);
-  hipError_t e = hipHostMalloc(&b.p, cap, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) {
-    b.cap = cap;
-    std::memset(b.p, 0, cap);
-  }
-  return e;
-}
+sr_status hip_fail(sr_ctx* ctx, hipError_t e, const char* what) { return sr::hip_fail(ctx->err, e, what); }
 
 // Run tags of every context of the process: a tag is never reused while the
 // process lives (2^32 runs), so words a freed context left behind cannot match.
@@ -1139,6 +1084,9 @@ sr_status sr_create(int32_t device, sr_ctx** out) {
     delete ctx;
     return SR_ERR_HIP;
   }
+  ctx->query.device = device;
+  ctx->query.stream = ctx->stream;
+  ctx->query.err = &ctx->err;
   if (const char* path = std::getenv("SR_K2_PROFILE")) ctx->prof_file = std::fopen(path, "ab");
   if (const char* m = std::getenv("SR_K2_MODE")) ctx->k2_mode = std::atoi(m) == 1 ? 1 : 0;
   if (const char* m = std::getenv("SR_NODE_PATCH")) ctx->node_patch = std::atoi(m) != 0;
@@ -1176,7 +1124,8 @@ void sr_destroy(sr_ctx* ctx) {
   }
   for (DevBuf* b : {&ctx->out_node, &ctx->out_status, &ctx->out_bytes, &ctx->dmin, &ctx->prof,
                     &ctx->scratch, &ctx->seq_status, &ctx->seq_node, &ctx->seq_off, &ctx->pdb_need, &ctx->pdb_remaining,
-                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->x_in, &ctx->x_out, &ctx->x_view, &ctx->e_scratch})
+                    &ctx->pdb_refused, &ctx->pdb_win, &ctx->query.x_in, &ctx->query.x_out, &ctx->query.x_view,
+                    &ctx->query.e_scratch})
     if (b->p) (void)hipFree(b->p);
   if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -1185,8 +1134,8 @@ void sr_destroy(sr_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->out_cycles.p) (void)hipFree(ctx->out_cycles.p);
   for (HostBuf* b : {&ctx->h_result, &ctx->h_status, &ctx->h_node, &ctx->h_bytes, &ctx->h_early, &ctx->h_comm,
-                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb, &ctx->hx_in, &ctx->hx_out,
-                     &ctx->hx_view})
+                     &ctx->h_seq_status, &ctx->h_seq_node, &ctx->h_seq_off, &ctx->h_pdb, &ctx->query.hx_in,
+                     &ctx->query.hx_out, &ctx->query.hx_view})
     if (b->p) (void)hipHostFree(b->p);
   for (auto& sl : ctx->slots) {
     if (sl->arena.p) (void)hipFree(sl->arena.p);
@@ -1564,474 +1513,6 @@ sr_status sr_can_drain_node(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cl
   }
   if (out_node_of_pod)
     for (int32_t i = 0; i < n; ++i) out_node_of_pod[i] = map[i];
-  return SR_OK;
-}
-
-// sr_explain_pods.  Each pod is a candidate of its own, encoded by the
-// context's explain encoder (x_enc: tags on), so a pod has no earlier pod of
-// its candidate and every filter is a static atom.  The call uploads what its
-// kernel reads -- the atom rows, the node free values of this encode, the
-// explain programs, the pods -- into one buffer of its own; nothing of the
-// planning side is read, written or re-encoded.
-// sr_explain_plan's batched pass is the same call with `pq`: pods are its
-// stop pods, pod i carries the context list pq->off[i] and the kernel is
-// explain_plan.hip's, which reads the lists and the nodes' pod slack from the
-// same buffer.  `slot` (nullptr: i) is where pod i's results go in `out`.
-// sr_shortfall_pods / sr_shortfall_plan are the same call with `sh`: the
-// sibling kernels (k_shortfall, k_shortfall_plan) run in place of the explain
-// kernels, read the nodes' pod slack in 64 bits (node_left, in the place of
-// node_slack) and leave per-block partials that k_shortfall_close closes on
-// the same stream; `out` gets what it gets without `sh`.
-// sr_node_view_pods / sr_node_view_plan are the same call with `view` (`out` and `sh` are then not looked
-// at): the kernels of node_view.hip run in place of the others, no per-query output is staged and nothing comes
-// down; every such pass of one call adds its active pods into the call's totals (view_begin, view_end).
-struct NodeViewCall {
-  sr_node_view_out* out;
-  int32_t per = 0;      // SR_NODE_VIEW_CHUNK
-  int32_t judged = 0;   // active pods of the passes so far
-};
-
-static sr_status explain(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                         sr_explain_out* out, const sr::PlanQueries* pq = nullptr, const int32_t* slot = nullptr,
-                         sr_shortfall_out* sh = nullptr, NodeViewCall* view = nullptr) {
-  if (n == 0) return SR_OK;
-  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
-  for (int32_t i = 0; i <= n; ++i) off[i] = i;
-  const sr_candidates cands{n, off.data(), pods, nullptr};
-  sr::Workload& w = ctx->x_wl;
-  ctx->x_enc.want_why = true;
-  w.reuse.drop();  // always a full encode: the tags belong to it
-  std::string err;
-  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &cands, &w, &err);
-  if (st != SR_OK) {
-    ctx->err = err;
-    return st;
-  }
-  for (int32_t i = 0; i < n; ++i) {  // a fallback pod: nothing evaluated
-    const uint8_t fb = w.status_host[i] == SR_CAND_FALLBACK ? 1 : 0;
-    if (!view) sr::clear_slot(out, sh, static_cast<size_t>(slot ? slot[i] : i), static_cast<size_t>(w.n_spot), fb);
-    else if (view->out->fallback) view->out->fallback[slot ? slot[i] : i] = fb;
-  }
-  if (w.pod_src.empty()) return SR_OK;
-  sr::ExplainStage& x = ctx->x_stage;
-  if (view) {
-    const sr::NodeViewAsk ask{slot, view->per};
-    st = x.plan(w, ctx->x_enc.node_free, snap, pq, true, false, false, &ctx->err, &ask);
-  } else {
-    st = x.plan(w, ctx->x_enc.node_free, snap, pq, sh != nullptr, out->node_mask != nullptr, sh && sh->node_short,
-                &ctx->err);
-  }
-  if (st != SR_OK) return st;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
-  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
-  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().dev_out_bytes));
-  x.pack(static_cast<char*>(ctx->hx_in.p));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (view) {  // (the totals were zeroed by view_begin and stay on the device until view_end)
-    if (static_cast<size_t>(w.n_spot) != snap->nodes.size()) {
-      ctx->err = "node view: the encode's spot nodes are not the snapshot's";
-      return SR_ERR_STATE;
-    }
-    sr::ExplainPlanArgs vpa;
-    sr::NodeViewArgs na;
-    x.view_args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p),
-                static_cast<char*>(ctx->x_view.p), &vpa, &na);
-    HIP_TRY(ctx, sr::launch_node_view(vpa, na, ctx->stream));
-    view->judged += x.n_pods();
-    return SR_OK;
-  }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
-  sr::ExplainPlanArgs pa;
-  sr::ShortfallArgs sa;
-  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), &pa, &sa);
-  if (pq && sh) HIP_TRY(ctx, sr::launch_shortfall_plan(pa, sa, ctx->stream));
-  else if (pq) HIP_TRY(ctx, sr::launch_explain_plan(pa, ctx->stream));
-  else if (sh) HIP_TRY(ctx, sr::launch_shortfall(pa.x, sa, ctx->stream));
-  else HIP_TRY(ctx, sr::launch_explain(pa.x, ctx->stream));
-  if (sh) HIP_TRY(ctx, sr::launch_shortfall_close(x.n_pods(), sa, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  x.unpack(static_cast<const char*>(ctx->hx_out.p), slot, out, sh);
-  return SR_OK;
-}
-
-static bool explain_out_ok(const sr_explain_out* out) { return out && out->feasible && out->first && out->counts; }
-
-static bool view_out_ok(const sr_node_view_out* o) {
-  return o && o->judged && o->admits && o->near && o->refuses && o->sole && o->sole_min && o->sole_at;
-}
-
-// The caller's arrays as of no judged query, and the call's totals zeroed on the stream (once a call).
-static sr_status view_begin(sr_ctx* ctx, const sr_snapshot* snap, NodeViewCall* view, bool device) {
-  const size_t ns = snap->nodes.size();
-  sr::node_view_clear(view->out, ns);
-  if (const char* b = std::getenv("SR_NODE_VIEW_CHUNK")) view->per = std::max(0, std::atoi(b));
-  if (!device || ns == 0) return SR_OK;
-  const size_t bytes = sr::node_view_layout(static_cast<size_t>(sr::node_view_stride(static_cast<int32_t>(ns))), 1).bytes;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the totals of the call before)
-  HIP_TRY(ctx, dev_reserve(ctx->x_view, bytes));
-  HIP_TRY(ctx, host_reserve(ctx->hx_view, bytes));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->x_view.p, 0, bytes, ctx->stream));
-  return SR_OK;
-}
-
-// The totals down in one copy and into the caller's arrays.
-static sr_status view_end(sr_ctx* ctx, const sr_snapshot* snap, NodeViewCall* view) {
-  const size_t ns = snap->nodes.size();
-  *view->out->judged = view->judged;
-  if (view->judged == 0 || ns == 0) return SR_OK;
-  const size_t stride = static_cast<size_t>(sr::node_view_stride(static_cast<int32_t>(ns)));
-  const size_t bytes = sr::node_view_layout(stride, 1).bytes;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_view.p, ctx->x_view.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  sr::node_view_unpack(static_cast<const char*>(ctx->hx_view.p), stride, ns, view->out);
-  return SR_OK;
-}
-
-sr_status sr_explain_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                          sr_explain_out* out) {
-  if (!ctx || !snap || !cluster || n < 0 || !explain_out_ok(out) || (n > 0 && !pods)) return SR_ERR_INVALID_ARG;
-  return explain(ctx, snap, cluster, pods, n, out);
-}
-
-sr_status sr_explain_candidate(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                               const int32_t* node_of_pod, int32_t at_pod, sr_explain_out* out) {
-  if (!ctx || !snap || !cluster || n < 0 || !explain_out_ok(out) || !pods || !node_of_pod) return SR_ERR_INVALID_ARG;
-  if (snap->forked) return SR_ERR_STATE;
-  if (at_pod < 0 || at_pod >= n) return SR_ERR_INVALID_ARG;
-  const int32_t n_spot = static_cast<int32_t>(snap->nodes.size());
-  for (int32_t k = 0; k <= at_pod; ++k)
-    if (pods[k] < 0 || pods[k] >= cluster->pods.n || (k < at_pod && (node_of_pod[k] < 0 || node_of_pod[k] >= n_spot)))
-      return SR_ERR_INVALID_ARG;
-  // Fork; the earlier pods where the plan put them (rescheduler.go:366): base
-  // pods now, so what they do to pods[at_pod] is static atoms; Revert
-  sr_status st = sr_snapshot_fork(snap);
-  if (st != SR_OK) return st;
-  for (int32_t k = 0; k < at_pod; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], node_of_pod[k]);
-  st = explain(ctx, snap, cluster, pods + at_pod, 1, out);
-  const sr_status rv = sr_snapshot_revert(snap);
-  return st != SR_OK ? st : rv;
-}
-
-static bool shortfall_out_ok(const sr_shortfall_out* sh) {
-  return sh && sh->near && sh->only_nodes && sh->only_min && sh->only_at;
-}
-
-// An sr_explain_out of the call's own where the caller of sr_shortfall_* wants none.
-struct OwnExplainOut {
-  std::vector<int32_t> feasible, first, counts;
-  sr_explain_out out{};
-  explicit OwnExplainOut(int32_t n) : feasible(std::max(n, 1)), first(std::max(n, 1)), counts(size_t(std::max(n, 1)) * SR_WHY_COUNT) {
-    out.feasible = feasible.data();
-    out.first = first.data();
-    out.counts = counts.data();
-  }
-};
-
-// sr_explain_plan.  The plain contexts (explain_plan.hpp) go through one
-// encode of their stop pods against the base snapshot, one upload, one launch
-// and one download; every other asked candidate through Fork / AddPod /
-// explain / Revert, as sr_explain_candidate does it.  A stop pod the batched
-// encode hands back as fallback is asked again on its own when the batch held
-// other pods: candidates of one encode share the state word's host-port bits,
-// so only an encode of its own tells "outside the encoded set" for certain.
-// (sr_shortfall_plan is this with `sh`)
-// (sr_node_view_plan is this with `view`: the batched pass and every SINGLE candidate add into the same totals)
-static sr_status explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                              const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how,
-                              sr_shortfall_out* sh, NodeViewCall* view = nullptr) {
-  const int32_t nc = cands->n_cand;
-  if (nc > 0 && (!cands->cand_pod_off || !cands->cand_pods || !at_pod)) return SR_ERR_INVALID_ARG;
-  if (snap->forked) return SR_ERR_STATE;
-  // (the queries are built apart from the context: an argument error returns before the context is looked at)
-  sr::PlanQueries pq;
-  sr_status st = sr::plan_queries(snap, cluster, cands, at_pod, node_of_pod, &pq);
-  if (st != SR_OK) return st;
-  const size_t ns = snap->nodes.size();
-  const int32_t nb = static_cast<int32_t>(pq.batched.size());
-  if (view) {
-    bool asked = false;
-    for (int32_t c = 0; c < nc; ++c) asked = asked || pq.how[c] != SR_EXPLAIN_NONE;
-    st = view_begin(ctx, snap, view, asked);
-    if (st != SR_OK) return st;
-    if (view->out->fallback) std::fill_n(view->out->fallback, nc, uint8_t(0));
-  } else {
-    for (int32_t c = 0; c < nc; ++c)  // not asked: as a fallback pod, but fallback = 0
-      if (pq.how[c] == SR_EXPLAIN_NONE) sr::clear_slot(out, sh, static_cast<size_t>(c), ns, 0);
-  }
-  st = explain(ctx, snap, cluster, pq.pods.data(), nb, out, &pq, pq.batched.data(), sh, view);
-  if (st != SR_OK) return st;
-  if (nb > 1)
-    for (int32_t i = 0; i < nb; ++i)
-      if (ctx->x_wl.status_host[i] == SR_CAND_FALLBACK) pq.how[pq.batched[i]] = SR_EXPLAIN_SINGLE;
-  const int32_t* off = cands->cand_pod_off;
-  for (int32_t c = 0; c < nc; ++c) {
-    if (pq.how[c] != SR_EXPLAIN_SINGLE) continue;
-    st = sr_snapshot_fork(snap);
-    if (st != SR_OK) return st;
-    const int32_t* pods = cands->cand_pods + off[c];
-    // (node_of_pod may be NULL when no asked candidate has an earlier pod)
-    const int32_t* map = node_of_pod ? node_of_pod + (off[c] - off[0]) : nullptr;
-    for (int32_t k = 0; k < at_pod[c]; ++k) sr::snapshot_add_pod(snap, cluster, pods[k], map[k]);
-    st = explain(ctx, snap, cluster, pods + at_pod[c], 1, out, nullptr, &c, sh, view);
-    const sr_status rv = sr_snapshot_revert(snap);
-    if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
-  }
-  if (view) {
-    st = view_end(ctx, snap, view);
-    if (st != SR_OK) return st;
-  }
-  if (out_how) std::copy(pq.how.begin(), pq.how.end(), out_how);
-  return SR_OK;
-}
-
-sr_status sr_explain_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                          const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* out, uint8_t* out_how) {
-  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !explain_out_ok(out)) return SR_ERR_INVALID_ARG;
-  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, out, out_how, nullptr);
-}
-
-sr_status sr_shortfall_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                            sr_explain_out* why, sr_shortfall_out* out) {
-  if (!ctx || !snap || !cluster || n < 0 || !shortfall_out_ok(out) || (why && !explain_out_ok(why)) || (n > 0 && !pods))
-    return SR_ERR_INVALID_ARG;
-  if (why) return explain(ctx, snap, cluster, pods, n, why, nullptr, nullptr, out);
-  OwnExplainOut own(n);
-  return explain(ctx, snap, cluster, pods, n, &own.out, nullptr, nullptr, out);
-}
-
-sr_status sr_shortfall_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                            const int32_t* at_pod, const int32_t* node_of_pod, sr_explain_out* why, sr_shortfall_out* out,
-                            uint8_t* out_how) {
-  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !shortfall_out_ok(out) || (why && !explain_out_ok(why)))
-    return SR_ERR_INVALID_ARG;
-  if (why) return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, why, out_how, out);
-  OwnExplainOut own(cands->n_cand);
-  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, &own.out, out_how, out);
-}
-
-sr_status sr_node_view_pods(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const int32_t* pods, int32_t n,
-                            sr_node_view_out* out) {
-  if (!ctx || !snap || !cluster || n < 0 || !view_out_ok(out) || (n > 0 && !pods)) return SR_ERR_INVALID_ARG;
-  NodeViewCall view{out};
-  sr_status st = view_begin(ctx, snap, &view, n > 0);
-  if (st != SR_OK) return st;
-  st = explain(ctx, snap, cluster, pods, n, nullptr, nullptr, nullptr, nullptr, &view);
-  return st != SR_OK ? st : view_end(ctx, snap, &view);
-}
-
-sr_status sr_node_view_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                            const int32_t* at_pod, const int32_t* node_of_pod, sr_node_view_out* out, uint8_t* out_how) {
-  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !view_out_ok(out)) return SR_ERR_INVALID_ARG;
-  NodeViewCall view{out};
-  return explain_plan(ctx, snap, cluster, cands, at_pod, node_of_pod, nullptr, out_how, nullptr, &view);
-}
-
-// sr_blockers_plan's batched pass: the pods of every candidate that is plain as a whole (blockers.hpp), encoded
-// as single-pod candidates by the explain encoder against the snapshot as it is; one upload, one launch of
-// k_blockers (a wave a candidate), one download.  A candidate the encode hands a fallback pod back for leaves
-// the batch (ways->how becomes SINGLE), for the reason given above explain_plan.
-static sr_status blockers_batched(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster,
-                                  const sr_candidates* cands, sr::BlockerWays* ways, sr_blockers_out* out) {
-  std::vector<int32_t> flat;
-  sr::blockers_flat(cands, *ways, &flat);
-  if (flat.empty()) {  // (asked candidates without pods)
-    for (int32_t c : ways->batched) out->blockers[c] = 0;
-    return SR_OK;
-  }
-  const int32_t n = static_cast<int32_t>(flat.size());
-  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
-  for (int32_t i = 0; i <= n; ++i) off[i] = i;
-  const sr_candidates singles{n, off.data(), flat.data(), nullptr};
-  sr::Workload& w = ctx->x_wl;
-  ctx->x_enc.want_why = true;
-  w.reuse.drop();  // always a full encode: the tags belong to it
-  std::string err;
-  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &singles, &w, &err);
-  if (st != SR_OK) {
-    ctx->err = err;
-    return st;
-  }
-  sr::BlockersStage& x = ctx->b_stage;
-  st = x.plan(w, ctx->x_enc.node_free, snap, cluster, cands, ways, out->counts != nullptr, &ctx->err);
-  if (st != SR_OK || x.n_cand() == 0) return st;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
-  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
-  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().out_bytes));
-  x.pack(static_cast<char*>(ctx->hx_in.p));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (x.at().zero_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
-  sr::BlockersArgs ba;
-  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), &ba);
-  HIP_TRY(ctx, sr::launch_blockers(ba, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  x.unpack(static_cast<const char*>(ctx->hx_out.p), cands, out);
-  return SR_OK;
-}
-
-// ... and one SINGLE candidate: the loop of the contract itself, every pod explained alone against the forked
-// snapshot that holds the pods placed before it.
-static sr_status blockers_single(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                                 int32_t c, sr_blockers_out* out) {
-  const int32_t* off = cands->cand_pod_off;
-  const int32_t* pods = cands->cand_pods + off[c];
-  const int32_t np = off[c + 1] - off[c];
-  const size_t p0 = static_cast<size_t>(off[c] - off[0]);
-  sr_status st = sr_snapshot_fork(snap);
-  if (st != SR_OK) return st;
-  OwnExplainOut own(1);
-  uint8_t fb = 0;
-  own.out.fallback = &fb;
-  int32_t blockers = 0, first = -1;
-  for (int32_t k = 0; k < np && st == SR_OK && !fb; ++k) {
-    st = explain(ctx, snap, cluster, pods + k, 1, &own.out);
-    if (st != SR_OK || fb) break;
-    out->node_of_pod[p0 + k] = own.first[0];
-    if (own.first[0] >= 0) {
-      sr::snapshot_add_pod(snap, cluster, pods[k], own.first[0]);
-      continue;
-    }
-    ++blockers;
-    if (first < 0) first = k;
-    if (out->counts) std::copy_n(own.counts.data(), SR_WHY_COUNT, out->counts + (p0 + k) * SR_WHY_COUNT);
-  }
-  const sr_status rv = sr_snapshot_revert(snap);
-  if (st != SR_OK || rv != SR_OK) return st != SR_OK ? st : rv;
-  if (fb) {
-    sr::blockers_clear(cands, c, 1, out);
-  } else {
-    out->blockers[c] = blockers;
-    out->first[c] = first;
-  }
-  return SR_OK;
-}
-
-sr_status sr_blockers_plan(sr_ctx* ctx, sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* cands,
-                           const int32_t* ask, sr_blockers_out* out, uint8_t* out_how) {
-  if (!ctx || !snap || !cluster || !cands || cands->n_cand < 0 || !out || !out->blockers || !out->first)
-    return SR_ERR_INVALID_ARG;
-  const int32_t nc = cands->n_cand;
-  if (nc == 0) return SR_OK;
-  if (!cands->cand_pod_off || !ask) return SR_ERR_INVALID_ARG;
-  const int32_t* off = cands->cand_pod_off;
-  if (off[nc] < off[0] || (off[nc] > off[0] && (!cands->cand_pods || !out->node_of_pod))) return SR_ERR_INVALID_ARG;
-  if (snap->forked) return SR_ERR_STATE;
-  // (the ways are decided apart from the context: an argument error returns before the context is looked at)
-  sr::BlockerWays ways;
-  sr_status st = sr::blockers_ways(snap, cluster, cands, ask, &ways);
-  if (st != SR_OK) return st;
-  for (int32_t c = 0; c < nc; ++c) sr::blockers_clear(cands, c, 0, out);
-  st = blockers_batched(ctx, snap, cluster, cands, &ways, out);
-  if (st != SR_OK) return st;
-  for (int32_t c = 0; c < nc; ++c) {
-    if (ways.how[c] != SR_EXPLAIN_SINGLE) continue;
-    st = blockers_single(ctx, snap, cluster, cands, c, out);
-    if (st != SR_OK) return st;
-  }
-  if (out_how) std::copy(ways.how.begin(), ways.how.end(), out_how);
-  return SR_OK;
-}
-
-// One pass of sr_evacuate_plan over the scenarios `ids` (all JUDGED by the rule): their pods encoded as
-// single-pod candidates by the explain encoder against the standing snapshot; one upload, one launch of
-// k_evacuate (a block of waves a scenario, grid-stride), one download.  A scenario the encode hands a fallback
-// pod back for is not planned and appended to *fell.
-static sr_status evacuate_pass(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* scen,
-                               const int32_t* lost_off, const int32_t* lost_pos, const std::vector<int32_t>& ids,
-                               std::vector<int32_t>* fell, sr_evacuate_out* out) {
-  std::vector<int32_t> flat;
-  sr::evacuate_flat(scen, ids, &flat);
-  if (flat.empty()) {  // (scenarios without pods)
-    for (int32_t s : ids) {
-      out->stranded[s] = 0;
-      if (out->how) out->how[s] = SR_EVAC_JUDGED;
-    }
-    return SR_OK;
-  }
-  const int32_t n = static_cast<int32_t>(flat.size());
-  std::vector<int32_t> off(static_cast<size_t>(n) + 1);
-  for (int32_t i = 0; i <= n; ++i) off[i] = i;
-  const sr_candidates singles{n, off.data(), flat.data(), nullptr};
-  sr::Workload& w = ctx->x_wl;
-  ctx->x_enc.want_why = true;
-  w.reuse.drop();  // always a full encode: the tags belong to it
-  std::string err;
-  sr_status st = sr::encode_workload(&ctx->x_enc, snap, cluster, &singles, &w, &err);
-  if (st != SR_OK) {
-    ctx->err = err;
-    return st;
-  }
-  sr::EvacuateStage& x = ctx->e_stage;
-  st = x.plan(w, ctx->x_enc.node_free, snap, cluster, scen, lost_off, lost_pos, ids, out->counts != nullptr, fell,
-              &ctx->err);
-  if (st != SR_OK || x.n_scen() == 0) return st;
-  int32_t blocks = 0, waves = 0;
-  sr::evacuate_shape(x.n_scen(), std::getenv("SR_EVAC_GRID"), std::getenv("SR_EVAC_WAVES"), &blocks, &waves);
-  const sr::EvacuateScratch sc = sr::evacuate_scratch(x.n_pad(), blocks);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers of the call before)
-  HIP_TRY(ctx, host_reserve(ctx->hx_in, x.at().in_bytes));
-  HIP_TRY(ctx, host_reserve(ctx->hx_out, x.at().out_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_in, x.at().in_bytes));
-  HIP_TRY(ctx, dev_reserve(ctx->x_out, x.at().out_bytes));
-  if (sc.bytes > ctx->e_scratch.cap) ctx->e_scratch_zero = false;
-  HIP_TRY(ctx, dev_reserve(ctx->e_scratch, sc.bytes));
-  if (!ctx->e_scratch_zero && ctx->e_scratch.p)
-    HIP_TRY(ctx, hipMemsetAsync(ctx->e_scratch.p, 0, ctx->e_scratch.cap, ctx->stream));
-  ctx->e_scratch_zero = false;  // until the launch is known to have finished
-  x.pack(static_cast<char*>(ctx->hx_in.p));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->x_in.p, ctx->hx_in.p, x.at().in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (x.at().zero_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->x_out.p, 0, x.at().zero_bytes, ctx->stream));
-  sr::EvacuateArgs ea;
-  x.args(static_cast<const char*>(ctx->x_in.p), static_cast<char*>(ctx->x_out.p), static_cast<char*>(ctx->e_scratch.p),
-         blocks, waves, &ea);
-  HIP_TRY(ctx, sr::launch_evacuate(ea, blocks, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->hx_out.p, ctx->x_out.p, x.at().out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->e_scratch_zero = true;
-  x.unpack(static_cast<const char*>(ctx->hx_out.p), scen, out);
-  return SR_OK;
-}
-
-sr_status sr_evacuate_plan(sr_ctx* ctx, const sr_snapshot* snap, const sr_cluster* cluster, const sr_candidates* scen,
-                           const int32_t* lost_off, const int32_t* lost_pos, sr_evacuate_out* out) {
-  if (!ctx || !snap || !cluster || !scen || scen->n_cand < 0 || !out || !out->stranded || !out->first)
-    return SR_ERR_INVALID_ARG;
-  const int32_t nc = scen->n_cand;
-  if (nc == 0) return SR_OK;
-  if (!scen->cand_pod_off || !lost_off) return SR_ERR_INVALID_ARG;
-  const int32_t* off = scen->cand_pod_off;
-  if (off[nc] < off[0] || (off[nc] > off[0] && (!scen->cand_pods || !out->node_of_pod))) return SR_ERR_INVALID_ARG;
-  if (lost_off[nc] < lost_off[0] || (lost_off[nc] > lost_off[0] && !lost_pos)) return SR_ERR_INVALID_ARG;
-  if (snap->forked) return SR_ERR_STATE;
-  // (the rule is decided apart from the context: an argument error returns before the context is looked at)
-  sr::EvacuateWays ways;
-  sr_status st = sr::evacuate_ways(snap, cluster, scen, lost_off, lost_pos, &ways);
-  if (st != SR_OK) return st;
-  for (int32_t s = 0; s < nc; ++s) sr::evacuate_clear(scen, s, ways.how[s], out);
-  std::vector<int32_t> fell;
-  st = evacuate_pass(ctx, snap, cluster, scen, lost_off, lost_pos, ways.judged, &fell, out);
-  if (st != SR_OK) return st;
-  // candidates of one encode share the state word's host-port bits (see explain_plan): a scenario the shared
-  // encode handed a fallback pod back for is asked again alone before SR_EVAC_FALLBACK stands
-  for (int32_t s : fell) {
-    std::vector<int32_t> again;
-    if (ways.judged.size() > 1) {
-      st = evacuate_pass(ctx, snap, cluster, scen, lost_off, lost_pos, std::vector<int32_t>{s}, &again, out);
-      if (st != SR_OK) return st;
-    } else {
-      again.push_back(s);
-    }
-    if (!again.empty()) sr::evacuate_clear(scen, s, SR_EVAC_FALLBACK, out);
-  }
   return SR_OK;
 }
 

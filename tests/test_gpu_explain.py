@@ -208,15 +208,19 @@ def test_explain_candidate_against_plans(checker, seed):
         lib.sr_snapshot_destroy(h)
 
 
-def _steady_scenario():
+def _steady_scenario(scale=1, extra=()):
     """Eight 1000m nodes, the last four closed by a 950m base pod; three candidates of 600m pods; a
     950m filler.  Filling an open node leaves it the 50m the closed nodes have: no free value appears or
-    goes, so no threshold moves and the tick after it needs no K0."""
-    nodes = [N("n%d" % i, cpu=1000) for i in range(8)]
-    base = [[] for _ in range(4)] + [[used(cpu=950, name="b%d" % i)] for i in range(4)]
-    cands = [[P("c0-0", cpu=600)], [P("c1-0", cpu=600), P("c1-1", cpu=600)], [P("c2-%d" % k, cpu=600) for k in range(5)]]
+    goes, so no threshold moves and the tick after it needs no K0.
+    scale: that many times the nodes and the candidates, the last candidate of every three one pod longer than
+    the open nodes are many; extra: further query pods behind the filler (sc.qidx from the filler's index + 1)."""
+    nodes = [N("n%d" % i, cpu=1000) for i in range(8 * scale)]
+    base = [[] for _ in range(4 * scale)] + [[used(cpu=950, name="b%d" % i)] for i in range(4 * scale)]
+    cands = []
+    for g in range(scale):
+        cands += [[P("c%d-%d" % (3 * g + j, k), cpu=600) for k in range(n)] for j, n in enumerate((1, 2, 4 * scale + 1))]
     flat = [p for c in cands for p in c]
-    query = flat + [Pod("filler", containers=[Container(cpu_milli=950)])]
+    query = flat + [Pod("filler", containers=[Container(cpu_milli=950)])] + list(extra)
     n_base = sum(len(b) for b in base)
     sc = Scenario(nodes, base, query, stamps=[1000 + i for i in range(n_base + len(query))])
     cand_off = np.zeros(len(cands) + 1, np.int32)

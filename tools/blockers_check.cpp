@@ -50,6 +50,36 @@ int32_t slack_of(int64_t left) {
   return static_cast<int32_t>(std::max<int64_t>(-(1 << 30), std::min<int64_t>(left, 1 << 30)));
 }
 
+size_t up8(size_t b) { return (b + 7) & ~size_t(7); }
+
+// The two part tables against the documented layout, written out here: the input parts atoms, node_free, xoff,
+// xops, pods, cand_off, node_left
+// and the output parts counts (absent when not wanted), node_of_pod, one count per candidate, first, in that
+// order; each of the size the pass gives it, at the 8-byte boundary after the part before it (so no two overlap)
+// and a multiple of its element size; the byte counts the rounded ends; the zeroed prefix the counts.
+bool layout_ok(const sr::BlockersLayout& at, const sr::Workload& w, const sr::BlockersStage& st, bool with_counts) {
+  const size_t np = static_cast<size_t>(st.n_pods()), nk = static_cast<size_t>(st.n_cand()), n_pad = static_cast<size_t>(w.n_pad);
+  const size_t in_want[sr::BIN_PARTS] = {w.atoms.size() * 8, 3 * n_pad * 8, st.programs().off.size() * 4,
+                                       st.programs().ops.size() * 4, np * sizeof(sr::BlockerPod), (nk + 1) * 4, n_pad * 8};
+  const size_t in_elem[sr::BIN_PARTS] = {8, 8, 4, 4, 8, 4, 8};
+  const size_t out_want[sr::GOUT_PARTS] = {with_counts ? np * SR_WHY_COUNT * 4 : 0, np * 4, nk * 4, nk * 4};
+  bool ok = at.n_in == sr::BIN_PARTS;
+  size_t end = 0;
+  for (int i = 0; i < sr::BIN_PARTS; ++i) {
+    const sr::StagePart& p = at.in[i];
+    ok = ok && p.off == up8(end) && p.bytes == in_want[i] && p.elem == in_elem[i] && p.off % in_elem[i] == 0;
+    end = p.off + p.bytes;
+  }
+  ok = ok && at.in_bytes == up8(end);
+  end = 0;
+  for (int i = 0; i < sr::GOUT_PARTS; ++i) {
+    const sr::StagePart& p = at.out[i];
+    ok = ok && p.off == up8(end) && p.bytes == out_want[i] && p.elem == 4 && p.off % 4 == 0;
+    end = p.off + p.bytes;
+  }
+  return ok && at.out_bytes == up8(end) && at.zero_bytes == out_want[sr::GOUT_COUNTS];
+}
+
 // k_blockers through the argument pointers.
 void emulate(const sr::BlockersArgs& b) {
   const sr::ExplainArgs& a = b.x;
@@ -164,8 +194,9 @@ int check_call(int config, const sr_cluster& c, sr_snapshot* snap, const sr_cand
     long long left_batch = 0;
     for (int32_t i = 0; i < nc; ++i) left_batch += rule.how[i] == SR_EXPLAIN_BATCHED && ways.how[i] == SR_EXPLAIN_SINGLE;
     bool ok = at.zero_bytes == (with_counts ? static_cast<size_t>(st.n_pods()) * SR_WHY_COUNT * 4 : 0) &&
-              at.out_bytes >= at.first + static_cast<size_t>(st.n_cand()) * 4 && at.in_bytes % 8 == 0 &&
-              static_cast<size_t>(st.n_cand()) + left_batch == rule.batched.size();
+              at.out_bytes >= at.out[sr::GOUT_FIRST].off + static_cast<size_t>(st.n_cand()) * 4 && at.in_bytes % 8 == 0 &&
+              static_cast<size_t>(st.n_cand()) + left_batch == rule.batched.size() &&
+              layout_ok(at, w, st, with_counts != 0);
     char* in = static_cast<char*>(malloc(at.in_bytes));
     char* dev = static_cast<char*>(malloc(at.out_bytes));
     st.pack(in);

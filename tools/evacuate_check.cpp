@@ -169,6 +169,36 @@ long long first_fit_lost(const sr_cluster* c, const sr_snapshot* snap, const int
   return n;
 }
 
+size_t up8(size_t b) { return (b + 7) & ~size_t(7); }
+
+// The two part tables against the documented layout, written out here: the input parts atoms, node_free, xoff,
+// xops, pods, scen_off, lost_off, lost_pos, node_left
+// and the output parts counts (absent when not wanted), node_of_pod, one count per scenario, first, in that
+// order; each of the size the pass gives it, at the 8-byte boundary after the part before it (so no two overlap)
+// and a multiple of its element size; the byte counts the rounded ends; the zeroed prefix the counts.
+bool layout_ok(const sr::EvacuateLayout& at, const sr::Workload& w, const sr::EvacuateStage& st, bool with_counts, size_t n_lost) {
+  const size_t np = static_cast<size_t>(st.n_pods()), nk = static_cast<size_t>(st.n_scen()), n_pad = static_cast<size_t>(w.n_pad);
+  const size_t in_want[sr::EIN_PARTS] = {w.atoms.size() * 8, 3 * n_pad * 8, st.programs().off.size() * 4,
+                                       st.programs().ops.size() * 4, np * sizeof(sr::BlockerPod), (nk + 1) * 4, (nk + 1) * 4, n_lost * 4, n_pad * 8};
+  const size_t in_elem[sr::EIN_PARTS] = {8, 8, 4, 4, 8, 4, 4, 4, 8};
+  const size_t out_want[sr::GOUT_PARTS] = {with_counts ? np * SR_WHY_COUNT * 4 : 0, np * 4, nk * 4, nk * 4};
+  bool ok = at.n_in == sr::EIN_PARTS;
+  size_t end = 0;
+  for (int i = 0; i < sr::EIN_PARTS; ++i) {
+    const sr::StagePart& p = at.in[i];
+    ok = ok && p.off == up8(end) && p.bytes == in_want[i] && p.elem == in_elem[i] && p.off % in_elem[i] == 0;
+    end = p.off + p.bytes;
+  }
+  ok = ok && at.in_bytes == up8(end);
+  end = 0;
+  for (int i = 0; i < sr::GOUT_PARTS; ++i) {
+    const sr::StagePart& p = at.out[i];
+    ok = ok && p.off == up8(end) && p.bytes == out_want[i] && p.elem == 4 && p.off % 4 == 0;
+    end = p.off + p.bytes;
+  }
+  return ok && at.out_bytes == up8(end) && at.zero_bytes == out_want[sr::GOUT_COUNTS];
+}
+
 int check_call(int config, const sr_cluster& c, sr_snapshot* snap, const std::vector<int32_t>& spot,
                const int32_t* node_off, const int32_t* node_idx, const sr_candidates& scen,
                const std::vector<int32_t>& loff, const std::vector<int32_t>& lpos, Tally* t) {
@@ -209,8 +239,12 @@ int check_call(int config, const sr_cluster& c, sr_snapshot* snap, const std::ve
     }
     const sr::EvacuateLayout& at = st.at();
     bool ok = at.zero_bytes == (with_counts ? static_cast<size_t>(st.n_pods()) * SR_WHY_COUNT * 4 : 0) &&
-              at.out_bytes >= at.first + static_cast<size_t>(st.n_scen()) * 4 && at.in_bytes % 8 == 0 &&
+              at.out_bytes >= at.out[sr::GOUT_FIRST].off + static_cast<size_t>(st.n_scen()) * 4 && at.in_bytes % 8 == 0 &&
               static_cast<size_t>(st.n_scen()) + fell.size() == rule.judged.size();
+    size_t n_lost = 0;  // of the planned scenarios
+    for (int32_t s : rule.judged)
+      if (std::find(fell.begin(), fell.end(), s) == fell.end()) n_lost += static_cast<size_t>(loff[s + 1] - loff[s]);
+    ok = ok && layout_ok(at, w, st, with_counts != 0, n_lost);
     const sr::EvacuateScratch sc = sr::evacuate_scratch(st.n_pad(), 1);
     char* in = static_cast<char*>(malloc(at.in_bytes));
     char* dev = static_cast<char*>(malloc(at.out_bytes));

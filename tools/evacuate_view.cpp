@@ -13,7 +13,7 @@
 
 namespace {
 
-// One pass over the scenarios `ids`, as evacuate_pass of planner.cpp runs it.
+// One pass over the scenarios `ids`, as evacuate_pass of query.cpp runs it.
 sr_status view_pass(const sr_cluster* cluster, const sr_snapshot* snap, const sr_candidates* scen, const int32_t* lost_off,
                     const int32_t* lost_pos, const std::vector<int32_t>& ids, std::vector<int32_t>* fell,
                     sr_evacuate_out* out) {
